@@ -23,7 +23,7 @@ non-zero (never a silent single-rank run). `--scaling strong` (default) measures
 defined, the whole node at 10K patterns: every rank's engine runs the full program as its shard
 (sdh_config.shard_rank / shard_world): the P patterns split by pattern set (rank r runs patterns r,
 r+N, ...; c3: the partition keys are split instead, rank r owning |String.valueOf(key).hashCode() % N|
-== r). `--scaling weak` gives every GPU P patterns of its own; a strong N>1 run appends that as a
+== r). `--scaling weak` gives every GPU P patterns of its own; a strong N>1 `--full` run appends that as a
 second line (`weak_scaling`). The exchange is the library's (include/siddhi_hip.h): an RCCL
 communicator (sdh_comm_create, its id handed out over torch.distributed's gloo control plane), rank
 0's device batch broadcast to every rank by sdh_engine_push_bcast inside the timed region.
@@ -31,7 +31,14 @@ torch.distributed (gloo) carries only control: barriers, the max over ranks, the
 `value` = pattern-events summed over ranks / the max over ranks of the timed region (barrier + device
 sync on both sides).
 
-Match expansion (`expansion` in the JSON line): a second engine in normal mode runs pushes of a
+A plain run does what the headline figure needs: engine, batches, warm-up, the timed steps, the line.
+`--full` adds the runs of their own after the timed steps -- the HBM ceiling calibration, the match
+expansion, host-ingest and push-latency legs, the CPU baseline and the weak-scaling line -- each still
+switched off by its `--no-*` option. `--dump-outputs DIR` writes what the last timed step handed out
+(dump_outputs) as float32 / float64 .npy files; the inputs are seeded by event index, so equal
+arguments give equal inputs and two builds compare output for output.
+
+Match expansion (`--full`; `expansion` in the JSON line): a second engine in normal mode runs pushes of a
 smaller batch followed by sdh_engine_poll_device -- the device R18 sort and the gather of the ABI
 tuples (query, key, ts, off, words) in HBM; with N GPUs sdh_engine_gather instead: every rank's
 R18-ordered tuples go to rank 0 over RCCL and are merged there on the device, timed per step.
@@ -90,9 +97,20 @@ def parse():
                          "~72 GB live in ~125 GB of rings)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-calibrate", action="store_true", help="skip the HBM copy / read ceiling measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the other legs: HBM ceiling calibration, match expansion, "
+                         "host ingest, push latency, the CPU baseline and (N>1, strong) the weak-scaling line; each "
+                         "can still be left out with its --no-* option. Without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step handed out (its device records, "
+                         "decoded) as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check: every rank prints {rank, local_rank, world_size} and exits (no GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the result line
+        args.no_expansion = args.no_ingest = args.no_latency = True
+        args.no_cpu_baseline = args.no_calibrate = args.no_weak_leg = True
+    return args
 
 
 def free_port():
@@ -405,6 +423,160 @@ def launches_per_step(prof, prof_dir):
         return 1
 
 
+DUMP_CAP = 64 << 20       # bytes --dump-outputs may write in all
+DUMP_EVENTS = 1 << 23     # matches_per_event: at most this many events (a seeded sample of a larger push)
+DUMP_SAMPLE_EVENTS = 32   # sampled_matches: every match of this many seeded trigger events
+DUMP_CHUNK_BLOCKS = 4096  # K_ratchet blocks decoded per pass (64 KiB blocks: 256 MiB)
+
+
+def _dev_copy(ptr, nbytes, dev):
+    """nbytes at the device pointer ptr -> a uint8 torch tensor (device-to-device copy)."""
+    import ctypes
+    import torch
+    t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if nbytes:
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        rc = hip.hipMemcpy(t.data_ptr(), ptr, nbytes, 3)  # hipMemcpyDeviceToDevice
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy of {nbytes} record bytes failed ({rc})")
+    return t
+
+
+def ratchet_outputs(rec, dev, seed=0):
+    """Part 1 of a push's device records (K_ratchet blocks, include/siddhi_hip.h sdh_records) decoded
+    from the descriptor's layout, DUMP_CHUNK_BLOCKS blocks at a time, into order-independent arrays:
+    matches per query, the sum of e2 - e1 per query, matches per trigger event, and every match
+    (query, e2 - seq_base, e2 - e1) of DUMP_SAMPLE_EVENTS seeded trigger events, sorted. Records carry
+    no delivery order, so these -- not the blocks as they lie in HBM -- compare from run to run."""
+    import torch
+    from siddhi_amd.engine import SDH_REC_4, SDH_REC_8
+    if rec.r_format not in (SDH_REC_4, SDH_REC_8):
+        log(f"--dump-outputs: K_ratchet record format {rec.r_format} is not decoded (counts only)")
+        return {}
+    nb, bb, n_ev = int(rec.r_blocks), int(rec.r_blk_bytes), int(rec.n_events)
+    W, M26 = bb // 4, (1 << 26) - 1
+    cnt_all = _dev_copy(rec.r_count, nb * 4, dev).view(torch.int32).long()
+    grp_all = _dev_copy(rec.r_group, nb * 4, dev).view(torch.int32).long()
+    if rec.r_format == SDH_REC_4:  # (a block with side < 0 in such a push holds 8-B records)
+        side_all = _dev_copy(rec.r_side, nb * 4, dev).view(torch.int32).long()
+    else:
+        side_all = torch.full((nb,), -1, dtype=torch.int64, device=dev)
+    ngr = int(grp_all.max().item()) + 1
+    lq = _dev_copy(rec.r_lane_query, ngr * 64 * 4, dev).view(torch.int32).long()
+    rng = np.random.default_rng(seed)
+    picked = torch.from_numpy(np.sort(rng.choice(n_ev, min(DUMP_SAMPLE_EVENTS, n_ev), replace=False))).to(dev)
+    per_lane = torch.zeros(ngr * 64, dtype=torch.int64, device=dev)
+    dsum_lane = torch.zeros(ngr * 64, dtype=torch.float64, device=dev)
+    per_event = torch.zeros(n_ev, dtype=torch.int64, device=dev)
+    sampled = []
+    col = torch.arange(W, device=dev)
+    col2 = torch.arange(W // 2, device=dev)
+
+    def tally(gl, d):  # gl: group * 64 + lane of each record; d: its e2 - e1
+        per_lane.add_(torch.bincount(gl, minlength=ngr * 64))
+        dsum_lane.add_(torch.bincount(gl, weights=d.double(), minlength=ngr * 64))
+
+    def check(e2, run, end):  # before anything is indexed by what was decoded
+        if len(e2) and (int(e2.max().item()) >= n_ev or int(run.min().item()) < 0 or int(end.max().item()) > W):
+            raise RuntimeError("--dump-outputs: a K_ratchet block does not decode by the documented layout")
+
+    if int(cnt_all.min().item()) < 0 or int(cnt_all.max().item()) > W or int(side_all.max().item()) > W // 2:
+        raise RuntimeError("--dump-outputs: K_ratchet block counts outside a block")
+    for b0 in range(0, nb, DUMP_CHUNK_BLOCKS):
+        b1 = min(nb, b0 + DUMP_CHUNK_BLOCKS)
+        n = b1 - b0
+        blk = _dev_copy(rec.r_base + b0 * bb, n * bb, dev).view(torch.int32).view(n, W)
+        cnt, grp, side = cnt_all[b0:b1], grp_all[b0:b1], side_all[b0:b1]
+        is4 = side >= 0
+        if bool(is4.any()):  # rec4 blocks: 4-B entries {d | lane << 26}, side entries {first, e2} from the end
+            c4 = torch.where(is4, cnt, torch.zeros_like(cnt))
+            valid = col[None, :] < c4[:, None]
+            ent = blk[valid].long() & 0xFFFFFFFF
+            gl = (grp * 64)[:, None].expand(n, W)[valid] + (ent >> 26)
+            tally(gl, ent & M26)
+            del valid, ent, gl
+            s4 = torch.where(is4, side, torch.zeros_like(side))
+            pairs = blk.view(n, W // 2, 2).flip(1)  # side entry j of block b = pairs[b, j] = (first, e2)
+            sp = pairs[col2[None, :] < s4[:, None]].long() & 0xFFFFFFFF  # rows in (block, j) order
+            del pairs
+            sb = torch.repeat_interleave(torch.arange(n, device=dev), s4)
+            first, e2 = sp[:, 0], sp[:, 1]
+            nxt = torch.empty_like(first)  # the entries of side entry j: first[j] .. first[j + 1] (the last: count)
+            nxt[:-1] = first[1:]
+            last = torch.ones_like(sb, dtype=torch.bool)
+            last[:-1] = sb[1:] != sb[:-1]
+            nxt[last] = cnt[sb[last]]
+            run = nxt - first
+            check(e2, run, nxt)
+            per_event.index_add_(0, e2, run)
+            sel = torch.isin(e2, picked) & (run > 0)
+            if bool(sel.any()):
+                rb, rf, rl, re2 = sb[sel], first[sel], run[sel], e2[sel]
+                k = torch.repeat_interleave(torch.arange(len(rl), device=dev), rl)
+                pos = rf[k] + torch.arange(len(k), device=dev) - (torch.cumsum(rl, 0) - rl)[k]
+                ent = blk[rb[k], pos].long() & 0xFFFFFFFF
+                sampled.append(torch.stack([lq[grp[rb[k]] * 64 + (ent >> 26)], re2[k], ent & M26], 1).cpu())
+        if bool((~is4).any()):  # 8-B records {e2 | lane << 26, low 32 bits of e1's seq}
+            c8 = torch.where(is4, torch.zeros_like(cnt), cnt)
+            valid = col2[None, :] < c8[:, None]
+            v = blk.view(n, W // 2, 2)[valid].long() & 0xFFFFFFFF
+            e2, lane = v[:, 0] & M26, v[:, 0] >> 26
+            d = ((rec.seq_base + e2) - v[:, 1]) & 0xFFFFFFFF
+            gl = (grp * 64)[:, None].expand(n, W // 2)[valid] + lane
+            tally(gl, d)
+            check(e2, e2, torch.zeros_like(e2))
+            per_event.index_add_(0, e2, torch.ones_like(e2))
+            sel = torch.isin(e2, picked)
+            if bool(sel.any()):
+                sampled.append(torch.stack([lq[gl[sel]], e2[sel], d[sel]], 1).cpu())
+        del blk
+    ok = lq >= 0
+    nq = int(lq.max().item()) + 1
+    per_query = torch.zeros(nq, dtype=torch.int64, device=dev).index_add_(0, lq[ok], per_lane[ok])
+    dsum = torch.zeros(nq, dtype=torch.float64, device=dev).index_add_(0, lq[ok], dsum_lane[ok])
+    if int(per_query.sum().item()) != int(rec.r_n) or int(per_event.sum().item()) != int(rec.r_n):
+        raise RuntimeError(f"--dump-outputs decoded {int(per_query.sum().item())} / {int(per_event.sum().item())} "
+                           f"K_ratchet records, the descriptor says {int(rec.r_n)}")
+    ev = per_event.cpu().numpy()
+    exact32 = int(ev.max()) < (1 << 24)  # counts that float32 holds exactly; float64 otherwise
+    keep = DUMP_EVENTS if exact32 else DUMP_EVENTS // 2
+    if n_ev > keep:  # a fixed, seeded sample of the push's events
+        ev = ev[np.sort(rng.choice(n_ev, keep, replace=False))]
+    rows = torch.cat(sampled).numpy() if sampled else np.zeros((0, 3), np.int64)
+    rows = rows[np.lexsort((rows[:, 2], rows[:, 0], rows[:, 1]))]  # by (e2, query, e2 - e1)
+    return {"matches_per_query": per_query.cpu().numpy().astype(np.float64),
+            "e1_distance_sum_per_query": dsum.cpu().numpy(),
+            "matches_per_event": ev.astype(np.float32 if exact32 else np.float64),
+            "sampled_matches": rows.astype(np.float64)}
+
+
+def dump_outputs(out_dir, eng, last_recs, dev, rank, world):
+    """--dump-outputs: what the last timed step handed to its caller -- the sdh_records of its pushes
+    (sdh_engine_poll_records) -- as float32 / float64 .npy files, DUMP_CAP bytes at most:
+    records_summary [pushes, 6] = (matches, K_ratchet / flat / K_chain matches, events, seq_base) of
+    each of the step's pushes; for the step's last push, whose records are still in HBM, the K_ratchet
+    part decoded (ratchet_outputs) and the library's order-independent digest of it (records_digest:
+    count, hash high and low 32 bits). Flat and K_chain parts are dumped as their counts. The inputs
+    are seeded by event index, so equal arguments give equal files."""
+    t0 = time.perf_counter()
+    out = {"records_summary": np.array([[r.n, r.r_n, r.f_n, r.c_n, r.n_events, r.seq_base]
+                                        for _, r in sorted(last_recs.items())], dtype=np.float64)}
+    rec = last_recs[max(last_recs)]
+    if rec.r_n > 0:
+        out.update(ratchet_outputs(rec, dev))
+        n, h = eng.debug_digest()
+        out["records_digest"] = np.array([n, h >> 32, h & 0xFFFFFFFF], dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_CAP:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_CAP}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "" if world == 1 else f"rank{rank}_"
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    log(f"--dump-outputs: {len(out)} arrays, {total / 1e6:.1f} MB in {out_dir} ({time.perf_counter() - t0:.1f} s)")
+
+
 def main():
     args = parse()
     rc = launch_ranks(args)
@@ -414,7 +586,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.dry_run:
-        print(json.dumps({"rank": rank, "local_rank": local, "world_size": world, "gpus": args.gpus}), flush=True)
+        # (one write per line: the ranks share the launcher's stdout)
+        sys.stdout.write(json.dumps({"rank": rank, "local_rank": local, "world_size": world, "gpus": args.gpus}) + "\n")
+        sys.stdout.flush()
         return
     import torch
     if local >= torch.cuda.device_count():
@@ -481,6 +655,8 @@ def main():
     pre = [local_batch(i) for i in range(args.warmup, n_batches)]
     torch.cuda.synchronize()
 
+    last_recs = {}  # stream -> the sdh_records of its latest push
+
     def make_step(engine, batches):
         def step(i):
             """One step: every stream's batch pushed once (broadcast from rank 0 by the library in
@@ -502,6 +678,7 @@ def main():
                 # the push's device records go to their consumer (sdh_engine_poll_records: the
                 # descriptor of the records in HBM; no device work)
                 rec = engine.poll_records()
+                last_recs[si] = rec  # (the descriptor the caller received; --dump-outputs reads the last one)
                 if len(per_stream) > 1 or i >= args.warmup:
                     kms, kby = engine.push_stats()  # (no device work inside the timed steps)
                     ms += kms
@@ -513,6 +690,8 @@ def main():
 
     elapsed, kern_ms, kern_bytes, rec_bytes, matches, pe = timed_steps(eng, make_step(eng, pre), args.warmup,
                                                                       args.steps, world, dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, last_recs, dev, rank, world)
     live = eng.stats().live_partials
     elapsed, matches, pe, live = reduce_run(elapsed, matches, pe, live, world, dist, cdev)
     value = pe / elapsed
