@@ -414,6 +414,9 @@ int sdh_spec_selftest(char* log, size_t cap);
 /* Test diagnostic: out[0] = the K_ratchet records the last push wrote, out[1] = an order-independent
  * hash of them (e2 seq, query, e1 seq), in either output mode (device records included). */
 int sdh_engine_debug_digest(sdh_engine* e, uint64_t* out);
+/* Test diagnostic: *out = the pushes so far whose K_ratchet records were written by the shared-pops
+ * form (the pops computed once per push; SDH_RATCHET_SHARED_MIN / SDH_RATCHET_NO_SHARED in debug). */
+int sdh_engine_debug_shared_pushes(sdh_engine* e, int64_t* out);
 /* Diagnostic: best-of-`iters` HBM bandwidth of a streaming copy (bytes read + written) and a
  * streaming read over `bytes`-sized buffers on `device`, in GB/s -- the measured ceiling the bench
  * reports its roofline fraction against beside the 8 TB/s peak. */

@@ -67,6 +67,12 @@ extern "C" hipError_t sdh_launch_chain(int n_states, int k, const sdh::ChainLaun
 extern "C" hipError_t sdh_launch_ratchet(int key_kind, int xmask, int full, int nf, int sim, int ML, int SC,
                                          const sdh::RatchetLaunch* L, hipStream_t s);
 extern "C" int sdh_ratchet_occupancy(int key_kind, int full, int nf, int ML, int sim);
+// the shared-pops form (nfa_ratchet_shared.hip)
+extern "C" size_t sdh_ratchet_shared_temp(int64_t n);
+extern "C" int sdh_ratchet_shared_occupancy();
+extern "C" hipError_t sdh_launch_ratchet_shared_pre(const sdh::SharedLaunch* S, const sdh::StreamBatch* B, int32_t* err,
+                                                    void* temp, size_t temp_bytes, hipStream_t s);
+extern "C" hipError_t sdh_launch_ratchet_shared(const sdh::RatchetLaunch* L, const sdh::SharedLaunch* S, hipStream_t s);
 extern "C" hipError_t sdh_launch_ratchet_summary(int key_kind, const sdh::StreamBatch* B, int attr, int conv,
                                                  int64_t n_tiles, uint64_t* tmax, uint64_t* tmin, uint8_t* thas,
                                                  hipStream_t s);
@@ -994,6 +1000,16 @@ struct sdh_engine {
   DevBuf<int64_t> d_rmatch;
   DevBuf<int32_t> d_blk_count, d_blk_next, d_blk_group;
   DevBuf<int32_t> d_blk_side;            // K_ratchet rec4 blocks: side entries (-1: an 8- / 16-B block)
+  // shared-pops form (nfa_ratchet_shared.hip): the pre-pass's tree, N(i) keys / values (unsorted and
+  // sorted), pairs, counts, sort scratch, and the groups' carried matches
+  DevBuf<float> d_shtree;
+  DevBuf<uint32_t> d_shkv, d_shcnt;
+  DevBuf<sdh::SharedPair> d_shpairs;
+  DevBuf<uint8_t> d_shtemp;
+  DevBuf<uint2> d_shcm;
+  DevBuf<int32_t> d_shcmn;
+  int64_t r_launches = 0;                // K_ratchet steps so far (SDH_RATCHET_SHARED_ALT)
+  int64_t r_shared_pushes = 0;           // pushes whose records the shared-pops form wrote
   int64_t r_rec4_reruns = 0;             // pushes re-run with 8-B records (a rec4 distance reached 2^26)
   DevBuf<unsigned long long> d_rtotal;  // device records: [0] entries, [2] bytes written
   int r_wide = 0;
@@ -1638,6 +1654,7 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
   e->r_kernel_bytes = 0;
   e->r_rec_bytes = 0;
   e->r_rec4 = 0;
+  ++e->r_launches;
   std::vector<int> gs;
   for (int g = 0; g < (int)e->rg.size(); ++g)
     if (e->rg[g].stream == stream) gs.push_back(g);
@@ -1677,7 +1694,29 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
     // in this batch
     auto lsim = [&](int g) { return e->rg[g].sim && !B.nul[e->rg[g].key_attr] ? 1 : 0; };
     auto lgate = [&](int g) { return e->rg[g].n_g > 0 ? 1 : 0; };  // K_gate groups (nfa_gate.hip)
-    auto lkey = [&](int g) { return std::make_tuple(lgate(g), e->rg[g].key_kind, e->rg[g].xmask, lsim(g)); };
+    // the shared-pops form (nfa_ratchet_shared.hip): SIM launches writing rec4 device
+    // records of a push large enough to repay the pre-pass. SDH_RATCHET_SHARED_MIN, C2 at 10K patterns
+    // in device-record mode, ms per push with the form on / off: 4,096 events 0.51 /
+    // 0.52, 16,384 0.67 / 0.60, 65,536 1.21 / 1.21, 262,144 2.68 / 3.38, 8M 61.7 / 85.7 -- the default
+    // lies between the tie and the first clear gain. SDH_RATCHET_NO_SHARED switches the form off;
+    // SDH_RATCHET_SHARED_ALT=k (tests) keeps it to every other K_ratchet step, the odd ones for k = 1
+    const bool rec4_ok = devrec && n <= ((int64_t)1 << 26) && !full && !no_rec4;
+    bool use_shared = rec4_ok && !sdh::knob("SDH_RATCHET_NO_SHARED");
+    if (use_shared) {
+      const char* mn = sdh::knob("SDH_RATCHET_SHARED_MIN");
+      use_shared = n >= std::max<int64_t>(1, mn ? atoll(mn) : 131072);
+      if (const char* alt = sdh::knob("SDH_RATCHET_SHARED_ALT")) use_shared = use_shared && (e->r_launches & 1) == (atoi(alt) & 1);
+    }
+    auto lshared = [&](int g) {
+      return use_shared && lsim(g) && !lgate(g) && B.width[e->rg[g].key_attr] == 4;
+    };
+    // (a shared-pops launch has one pre-pass, so it also holds one key column: eligibility is per group,
+    // and the shared groups' launches are cut by column and conversion as well)
+    auto lkey = [&](int g) {
+      const bool sh = lshared(g);
+      return std::make_tuple(lgate(g), e->rg[g].key_kind, e->rg[g].xmask, lsim(g), sh ? 1 : 0,
+                             sh ? e->rg[g].key_attr : -1, sh ? e->rg[g].key_conv : -1);
+    };
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lkey(a) < lkey(b); });
     for (size_t i0 = 0; i0 < order.size();) {
       size_t i1 = i0;
@@ -1689,16 +1728,21 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
       // 117.8 ms/step, 16,384 110.9, 32,768 103.3, 65,536 100.2, 131,072 100.8, 524,288 104.4
       double slots = e->r_waves;
       if (slots <= 0) {
-        const int occ = lgate(order[i0]) ? sdh_gate_occupancy(nf, nf)
+        const int occ = lshared(order[i0]) ? sdh_ratchet_shared_occupancy()
+                        : lgate(order[i0]) ? sdh_gate_occupancy(nf, nf)
                                          : sdh_ratchet_occupancy(e->rg[order[i0]].key_kind, full, nf, e->rML, lsim(order[i0]));
-        slots = 8.0 * (double)e->n_cu * std::max(1, occ);
+        // (the shared-pops form, whose items have no warm-up to repeat: 16 rounds. SDH_RATCHET_WAVES at
+        // C2's 8M-event step: 16,384 items 70.3 ms, 32,768 64.3, 8 rounds 61.7, 131,072 60.3, 262,144 61.2)
+        slots = (lshared(order[i0]) ? 16.0 : 8.0) * (double)e->n_cu * std::max(1, occ);
       }
       // chunks per chunkable group: as many as fit the item target (floor, not ceil: a partial
       // extra round of items runs as a nearly idle tail -- C2 at 10K once had 8,321 items for 8,192
       // slots, 128.7 ms/step, against 117.7 at 8,164), at least min_chunk events each. Groups
       // without `within` cannot chunk (no reverse-scan window) and hold one item each.
       int64_t n_chunkable = 0;
-      for (size_t i = i0; i < i1; ++i) n_chunkable += (!full && e->rg[order[i]].wmax >= 0) ? 1 : 0;
+      // (the shared-pops form's items need no warm-up: every group chunks, `within` or not)
+      const bool shared = lshared(order[i0]);
+      for (size_t i = i0; i < i1; ++i) n_chunkable += (shared || (!full && e->rg[order[i]].wmax >= 0)) ? 1 : 0;
       const int64_t free_slots = std::max<int64_t>(1, (int64_t)slots - ((int64_t)(i1 - i0) - n_chunkable));
       const int64_t c_fit = n_chunkable > 0 ? std::max<int64_t>(1, free_slots / n_chunkable) : 1;
       const int64_t c_min = std::max<int64_t>(1, n / std::max<int64_t>(1, min_chunk));
@@ -1706,7 +1750,9 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
         const int g = order[i];
         const RatchetGroup& G = e->rg[g];
         int64_t C = 1;
-        if (!full && G.wmax >= 0) {
+        if (shared) {
+          C = std::min(c_fit, c_min);
+        } else if (!full && G.wmax >= 0) {
           C = std::min(c_fit, c_min);
           // a chunk's warm-up walks its `within` window back from its first event: tiles whose best
           // key is dominated by the later ones are skipped on their summary, but flat or rising key
@@ -1763,6 +1809,10 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
       for (size_t r = 0; r < n_rows; ++r) {
         const auto& sp = e->r_sum_specs[r];
         if (sp[0] != stream) continue;
+        // (the shared-pops form has its own tree: a row only its groups read is not built)
+        bool read = false;
+        for (int g : gs) read = read || (e->rg[g].sum_slot == (int)r && !lshared(g));
+        if (!read) continue;
         HIPCHK(sdh_launch_ratchet_summary(sp[3], &B, sp[1], sp[2], n_tiles, e->d_tsmax.p + r * n_tiles,
                                           e->d_tsmin.p + r * n_tiles, e->d_tshas.p + r * n_tiles, e->stream));
       }
@@ -1805,7 +1855,44 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
       L.n_cells = nc;
     }
     e->r_placing = false;
-    int any_rec4 = 0;
+    int any_rec4 = 0, any_shared = 0;
+    // the shared-pops form's buffers for the launch of group g0
+    auto shared_setup = [&](int g0) {
+      SharedLaunch S{};
+      const RatchetGroup& G = e->rg[g0];
+      S.x = (const float*)B.col[G.key_attr];
+      S.n = n;
+      S.xm = G.xmask == sdh::CM_GT ? 0 : G.xmask == (sdh::CM_GT | sdh::CM_EQ) ? 1 : G.xmask == sdh::CM_LT ? 2 : 3;
+      int64_t tot = 0;
+      for (int64_t cur = n; cur > 64 && S.n_lvl < sdh::SH_LEVELS;) {
+        cur = (cur + 63) / 64;
+        S.lvl_n[S.n_lvl++] = cur;
+        tot += cur;
+      }
+      e->d_shtree.ensure((size_t)tot + 1);
+      tot = 0;
+      for (int k = 0; k < S.n_lvl; ++k) {
+        S.lvl[k] = e->d_shtree.p + tot;
+        tot += S.lvl_n[k];
+      }
+      e->d_shkv.ensure((size_t)n * 4);
+      S.nkey = e->d_shkv.p;
+      S.nval = e->d_shkv.p + n;
+      S.skey = e->d_shkv.p + 2 * n;
+      S.sval = e->d_shkv.p + 3 * n;
+      e->d_shpairs.ensure((size_t)n);
+      S.pairs = e->d_shpairs.p;
+      e->d_shcnt.ensure(2);
+      S.cnt = e->d_shcnt.p;
+      const size_t ng = e->rg.size();
+      e->d_shcm.ensure(ng * (size_t)e->rsmax * WAVE);
+      e->d_shcmn.ensure(2 * ng * WAVE);
+      S.cm = e->d_shcm.p;
+      S.cm_n = e->d_shcmn.p;
+      S.cs_n = e->d_shcmn.p + ng * WAVE;
+      e->d_shtemp.ensure(sdh_ratchet_shared_temp(n) + 16);
+      return S;
+    };
     // one launch per (key kind, orientation, SIM form)
     auto run = [&](const RatchetLaunch& L0) {
       for (int i0 = 0; i0 < n_items;) {
@@ -1824,7 +1911,14 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
         Ls.spillB = any64 ? e->d_rspillB.p + (size_t)i0 * e->rSC * WAVE : nullptr;
         Ls.rec4 = L0.rec4 && sim && !gate ? 1 : 0;  // (rec4 blocks come from the SIM form only)
         any_rec4 |= Ls.rec4;
-        if (gate) {
+        if (Ls.rec4 && !Ls.pcnt && !Ls.crow && lshared(g0)) {
+          // one pre-pass per launch = per (stream, key column, OP) of the push
+          const SharedLaunch S = shared_setup(g0);
+          HIPCHK(hipMemsetAsync(S.cnt, 0, 8, e->stream));
+          HIPCHK(sdh_launch_ratchet_shared_pre(&S, &B, e->d_err.p, e->d_shtemp.p, e->d_shtemp.n, e->stream));
+          HIPCHK(sdh_launch_ratchet_shared(&Ls, &S, e->stream));
+          any_shared = 1;
+        } else if (gate) {
           int ng = 0;
           for (int i = i0; i < i1; ++i) ng = std::max(ng, e->rg[e->ritems[i].g].n_g);
           HIPCHK(sdh_launch_gate(kk, xm, full, nf, ng, e->rSC, &Ls, e->stream));
@@ -1915,6 +2009,7 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
       ms += ms2;
     }
     for (int g : gs) e->rcur[g] ^= 1;
+    e->r_shared_pushes += any_shared;
     e->r_placing = placing;
     e->r_blk_taken = used;
     e->r_seq_base = B.seq_base;
@@ -4614,6 +4709,13 @@ int sdh_engine_debug_digest(sdh_engine* e, uint64_t* out) {
     d2h_sync(e, out, acc.p, 16);
     return SDH_OK;
   });
+}
+
+// Test diagnostic: pushes so far whose K_ratchet records the shared-pops form wrote
+int sdh_engine_debug_shared_pushes(sdh_engine* e, int64_t* out) {
+  if (!e || !out) return SDH_E_INVALID;
+  *out = e->r_shared_pushes;
+  return SDH_OK;
 }
 
 // The last push's device records (SDH_FLAG_DEVICE_MATCHES; formats: include/siddhi_hip.h sdh_records)

@@ -291,27 +291,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SIM ? 8 : 7)
     f_ptr[a] = pick(L.b.col, A0.attr); f_w[a] = pick(L.b.width, A0.attr); f_nul[a] = pick(L.b.nul, A0.attr);
     f_ptr2[a] = pick(L.b.col, A0.attr2); f_w2[a] = pick(L.b.width, A0.attr2); f_nul2[a] = pick(L.b.nul, A0.attr2);
   }
-  // SIM: the start atom's interval of sortable binary64 keys as binary32 bounds (x in [flo, fhi] iff
-  // the widened key is in the interval; idle lanes get an empty one)
+  // SIM: the start atom's interval as binary32 bounds (ratchet_common.h sim_bounds)
   float flo = 0.f, fhi = 0.f;
-  if constexpr (SIM) {
-    auto unsort = [](int64_t v) { return __longlong_as_double(v >= 0 ? v : (v ^ INT64_MAX)); };
-    if (!active || f_lo[0] > f_hi[0]) {
-      flo = __int_as_float(0x7f800000);   // +inf
-      fhi = __int_as_float((int)0xff800000u);  // -inf
-    } else {
-      const double lo = f_lo[0] <= INT64_MIN + 1 ? -__longlong_as_double(0x7ff0000000000000ll) : unsort(f_lo[0]);
-      const double hi = f_hi[0] == INT64_MAX ? __longlong_as_double(0x7ff0000000000000ll) : unsort(f_hi[0]);
-      // the least float >= lo and the greatest float <= hi (one ulp step from the nearest; from +-0
-      // the step is the least denormal of the right sign)
-      flo = (float)lo;
-      if (flo == 0.f && lo > 0.0) flo = __int_as_float(1);
-      else if ((double)flo < lo) flo = __int_as_float(__float_as_int(flo) + (flo > 0.f ? 1 : -1));
-      fhi = (float)hi;
-      if (fhi == 0.f && hi < 0.0) fhi = __int_as_float((int)0x80000001u);
-      else if ((double)fhi > hi) fhi = __int_as_float(__float_as_int(fhi) + (fhi > 0.f ? -1 : 1));
-    }
-  }
+  if constexpr (SIM) sim_bounds(G, lane, active, flo, fhi);
   const U TSENT = SIM ? (U)0x7fc00000u : (U)0;  // SIM: the top key of an empty deque (NaN)
   const void* k_ptr = pick(L.b.col, kattr);
   const uint8_t* k_nul = pick(L.b.nul, kattr);

@@ -242,6 +242,38 @@ struct RatchetLaunch {
   int32_t n_cells, cw;
 };
 
+// K_ratchet, shared-pops form (nfa_ratchet_shared.hip): the pops of the family depend only on
+// the key column and OP -- partial i is popped by N(i), the first later event j with `x_j OP x_i` --
+// so one pre-pass per push lists the pairs (i, N(i)) sorted by N(i), and each group only filters them.
+constexpr int SH_LEVELS = 5;  // 64-ary best-key tree over the key column (2^26 events: 4 levels)
+
+struct SharedPair {
+  uint32_t j, d;   // e2's batch offset; e2 - e1 in events
+  uint32_t key;    // e1's key (binary32 bits)
+  int32_t age;     // ts(e2) - ts(e1) (ordered batches spanning < 2^31 - 2 ms)
+};
+
+struct SharedLaunch {
+  const float* x;              // the key column (null-free binary32)
+  int64_t n;                   // batch events
+  int32_t xm;                  // OP: 0 >, 1 >=, 2 <, 3 <=
+  int32_t n_lvl;               // tree levels in use: level k holds the best (max for >, >=; min) key of
+  float* lvl[SH_LEVELS];       //   each 64 entries of level k - 1 (level -1: the events); NaN: none.
+  int64_t lvl_n[SH_LEVELS];    //   The top level has at most 64 entries
+  uint32_t* nkey;              // [n] N(i); n: no N (the closing staircase U); n + 1: NaN key
+  uint32_t* nval;              // [n] i
+  uint32_t* skey;              // the same, stably sorted by N: the pairs, then U oldest first
+  uint32_t* sval;
+  SharedPair* pairs;           // [cnt[0]] sorted by j
+  uint32_t* cnt;               // [0] pairs, [1] events of U
+  // carried partials (the groups' persisted deques): per lane the matches {e2 batch offset, e1 seq low
+  // bits} by ascending e2, [g][rsmax][64]; cm_n[g][64] their count, cs_n[g][64] the survivors already
+  // written to the next deques
+  uint2* cm;
+  int32_t* cm_n;
+  int32_t* cs_n;
+};
+
 // ------------------------------------------------------------------------------------------
 // K_gen launch (nfa_gen.hip): item = (segment of one key's events, group of 64 queries)
 // ------------------------------------------------------------------------------------------

@@ -232,6 +232,37 @@ __device__ __forceinline__ void f0_interval(int mask, bool f64, int64_t c, int64
   if (empty_lo || empty_hi) { lo = 1; hi = 0; }
 }
 
+// SIM (the C2 family's form; nfa_ratchet.hip): the start atom's interval of sortable binary64 keys as
+// binary32 bounds of one lane (x in [flo, fhi] iff the widened key is in the interval; idle lanes and
+// empty intervals get an empty one). Both forms of the SIM launch use it, so their start filters agree.
+__device__ __forceinline__ void sim_bounds(const RatchetGroup* G, int lane, bool active, float& flo, float& fhi) {
+  const RatchetAtom A0 = G->f0[0];
+  int m = A0.mask;
+  if (!A0.cur_left && !A0.cur2) {
+    const int lt = m & CM_LT, gt = m & CM_GT;
+    m = (m & (CM_EQ | CM_NOT)) | (lt ? CM_GT : 0) | (gt ? CM_LT : 0);
+  }
+  int64_t lo64, hi64;
+  bool neg;
+  f0_interval(m, A0.f64 != 0, G->f0c[0][lane & 63], lo64, hi64, neg);
+  auto unsort = [](int64_t v) { return __longlong_as_double(v >= 0 ? v : (v ^ INT64_MAX)); };
+  if (!active || lo64 > hi64) {
+    flo = __int_as_float(0x7f800000);
+    fhi = __int_as_float((int)0xff800000u);
+    return;
+  }
+  const double lo = lo64 <= INT64_MIN + 1 ? -__longlong_as_double(0x7ff0000000000000ll) : unsort(lo64);
+  const double hi = hi64 == INT64_MAX ? __longlong_as_double(0x7ff0000000000000ll) : unsort(hi64);
+  // the least float >= lo and the greatest float <= hi (one ulp step from the nearest; from +-0
+  // the step is the least denormal of the right sign)
+  flo = (float)lo;
+  if (flo == 0.f && lo > 0.0) flo = __int_as_float(1);
+  else if ((double)flo < lo) flo = __int_as_float(__float_as_int(flo) + (flo > 0.f ? 1 : -1));
+  fhi = (float)hi;
+  if (fhi == 0.f && hi < 0.0) fhi = __int_as_float((int)0x80000001u);
+  else if ((double)fhi > hi) fhi = __int_as_float(__float_as_int(fhi) + (fhi > 0.f ? -1 : 1));
+}
+
 __device__ __forceinline__ int64_t sat_add(int64_t a, int64_t b) {  // b >= 0
   return a > INT64_MAX - b ? INT64_MAX : a + b;
 }

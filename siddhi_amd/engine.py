@@ -112,7 +112,7 @@ EXPORTS = ["sdh_engine_create", "sdh_engine_push", "sdh_engine_flush", "sdh_engi
            "sdh_engine_push_stats", "sdh_comm_get_id", "sdh_comm_create", "sdh_comm_create_local",
            "sdh_comm_destroy", "sdh_comm_last_error", "sdh_engine_set_comm", "sdh_engine_push_bcast",
            "sdh_engine_gather", "sdh_engine_reserve", "sdh_engine_reserve_keys", "sdh_engine_poll_records",
-           "sdh_engine_records_compact"]
+           "sdh_engine_records_compact", "sdh_engine_debug_shared_pushes"]
 SDH_COMM_ID_BYTES = 128
 
 _lib = None
@@ -156,6 +156,7 @@ def load_library(path: str = LIB_PATH):
     lib.sdh_build_info.restype = ctypes.c_char_p
     lib.sdh_engine_push_stats.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     lib.sdh_engine_debug_digest.argtypes = [P, ctypes.POINTER(ctypes.c_uint64)]
+    lib.sdh_engine_debug_shared_pushes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
     lib.sdh_engine_set_strings.argtypes = [P, ctypes.c_int64, P, P, P]
     D = ctypes.POINTER(ctypes.c_double)
     lib.sdh_calibrate_hbm.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, D, D]
@@ -221,11 +222,11 @@ class HipEngine:
     def __init__(self, blob: bytes, device: int = 0, partials: int = 128, shard_rank: int = 0,
                  shard_world: int = 1, chunk_events: int = 0, stream_types=None, flags: int = 0,
                  gen_pool_states: int = 0, gen_pool_nodes: int = 0, gen_list_cap: int = 0,
-                 gen_max_keys: int = 0, debug=None):
+                 gen_max_keys: int = 0, debug=None, match_capacity: int = 0):
         self.lib = load_library()
         self._debug = debug_string(debug)
         cfg = SdhConfig(device=device, shard_rank=shard_rank, shard_world=shard_world,
-                        partials_per_inst=partials, max_batch=0, match_capacity=0,
+                        partials_per_inst=partials, max_batch=0, match_capacity=match_capacity,
                         chunk_events=chunk_events, flags=flags, gen_pool_states=gen_pool_states,
                         gen_pool_nodes=gen_pool_nodes, gen_list_cap=gen_list_cap, gen_pad=0,
                         gen_max_keys=gen_max_keys, debug=self._debug)
@@ -427,6 +428,12 @@ class HipEngine:
         out = (ctypes.c_uint64 * 2)()
         self._check(self.lib.sdh_engine_debug_digest(self.h, out))
         return int(out[0]), int(out[1])
+
+    def debug_shared_pushes(self):
+        """Pushes so far whose K_ratchet records the shared-pops form wrote (sdh_engine_debug_shared_pushes)."""
+        out = ctypes.c_int64()
+        self._check(self.lib.sdh_engine_debug_shared_pushes(self.h, ctypes.byref(out)))
+        return int(out.value)
 
     def state_bytes(self):
         """(live, reserved, directory) bytes of the sparse K_slab state (sdh_engine_state_bytes)."""
