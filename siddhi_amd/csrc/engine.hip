@@ -1,1071 +1,18 @@
-// engine.hip -- host side of libsiddhi_hip.so: IR lowering, HBM state management, batching,
-// chunk planning, NFA-step launches and match hand-off. Implements include/siddhi_hip.h.
+// engine.hip -- host side of libsiddhi_hip.so: plan selection, HBM state management, batching,
+// the K_gen / K_seq / K_part / K_slab passes and match hand-off. Implements include/siddhi_hip.h.
+// IR lowering is in engine_lower.hip, the K_chain and K_ratchet launches in engine_ratchet.hip, the
+// K_slab arena in engine_slab.hip (engine_int.h).
 //
-// The reference has no device boundary; this file is the GpuStateStreamRuntime half that replaces
+// The reference has no device boundary; the engine is the GpuStateStreamRuntime half that replaces
 // StateInputStreamParser's object graph (core/util/parser/StateInputStreamParser.java:77-398) with
 // device tables, and the receiver loop (core/query/input/*ProcessStreamReceiver.java) with one
 // batched launch per pushed event batch.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <chrono>
-#include <tuple>
-#include <array>
-#include <cmath>
-#include <map>
-#include <unordered_map>
-#include <memory>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include "../../include/siddhi_hip.h"
+#include "engine_int.h"
+#include "launchers.h"
 #include "chm_order.h"
-#include "comm.h"
-#include "knobs.h"
 #include "java_fmt.h"
-#include "gen_lower.h"
-#include "nfa_types.h"
 #include "slab_lower.h"
 #include "spec.h"
-
-extern "C" hipError_t sdh_launch_gen(const sdh::GenLaunch* L, hipStream_t s);
-extern "C" hipError_t sdh_launch_part(const sdh::PartLaunch* L, hipStream_t s);
-extern "C" hipError_t sdh_launch_seq(const sdh::SeqLaunch* L, hipStream_t s);
-extern "C" hipError_t sdh_launch_slab(const sdh::SlabLaunch* L, hipStream_t s);
-extern "C" hipError_t sdh_slab_rollback(uint64_t* dir, const uint64_t* journal, const uint64_t* journal_idx, int64_t n,
-                                        const long long* live_bak, long long* live, hipStream_t s);
-extern "C" hipError_t sdh_slab_move(uint64_t* dir, int64_t n_dir, int groups, const int32_t* group_ew,
-                                    uint32_t* const* src_ring, const int64_t* src_cap,
-                                    const unsigned long long* src_tail, int src_nsub, const unsigned long long* limit,
-                                    const uint8_t* active, uint32_t* const* dst_ring, const int64_t* dst_cap,
-                                    unsigned long long* dst_head, const unsigned long long* dst_tail, int dst_nsub,
-                                    int32_t* err, uint8_t* ring_err, hipStream_t s);
-extern "C" hipError_t sdh_slab_live_words_ring(const uint64_t* dir, int64_t n_dir, int groups, const int32_t* group_ew,
-                                               int nsub, unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_slab_live_words(const uint64_t* dir, int64_t n_dir, int groups, const int32_t* group_ew,
-                                          unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_seq_tail(const sdh::StreamBatch* b, int64_t* tail, int32_t tail_len, int32_t new_tail_len,
-                                   hipStream_t s);
-extern "C" hipError_t sdh_route_partition(const sdh::StreamBatch* B, int attr, int type, unsigned long long* tkey,
-                                          int32_t* tid, int64_t table_mask, int32_t* n_keys, int64_t* key_of_id,
-                                          int64_t key_cap, int64_t* key, uint32_t* kid, uint32_t* kid_sorted,
-                                          int32_t* idx, int32_t* idx_sorted, uint32_t* uniq, int32_t* cnt,
-                                          int32_t* off, int32_t* n_runs_dev, void* temp, size_t temp_bytes,
-                                          int32_t* err, int shard_rank, int shard_world, hipStream_t s);
-extern "C" size_t sdh_route_temp_bytes(int64_t n);
-extern "C" hipError_t sdh_gen_remap(const int32_t* lane_q, int group_base, int n_groups, int64_t blocks,
-                                    const sdh::kg::GLayout* oldL, const sdh::kg::GLayout* newL, const int32_t* o32,
-                                    const int64_t* o64, int64_t oB32, int64_t oB64, int32_t* n32, int64_t* n64,
-                                    int64_t nB32, int64_t nB64, hipStream_t s);
-
-extern "C" hipError_t sdh_launch_chain(int n_states, int k, const sdh::ChainLaunch* L, int n_blocks,
-                                       size_t lds, hipStream_t s);
-extern "C" hipError_t sdh_launch_ratchet(int key_kind, int xmask, int full, int nf, int sim, int ML, int SC,
-                                         const sdh::RatchetLaunch* L, hipStream_t s);
-extern "C" int sdh_ratchet_occupancy(int key_kind, int full, int nf, int ML, int sim);
-// the shared-pops form (nfa_ratchet_shared.hip)
-extern "C" size_t sdh_ratchet_shared_temp(int64_t n);
-extern "C" int sdh_ratchet_shared_occupancy();
-extern "C" hipError_t sdh_launch_ratchet_shared_pre(const sdh::SharedLaunch* S, const sdh::StreamBatch* B, int32_t* err,
-                                                    void* temp, size_t temp_bytes, hipStream_t s);
-extern "C" hipError_t sdh_launch_ratchet_shared(const sdh::RatchetLaunch* L, const sdh::SharedLaunch* S, hipStream_t s);
-extern "C" hipError_t sdh_launch_ratchet_summary(int key_kind, const sdh::StreamBatch* B, int attr, int conv,
-                                                 int64_t n_tiles, uint64_t* tmax, uint64_t* tmin, uint8_t* thas,
-                                                 hipStream_t s);
-extern "C" hipError_t sdh_append_ratchet(const int64_t* match, int blk_recs, int wide, const int32_t* blk_count,
-                                         const int32_t* blk_group, const int64_t* dst_off,
-                                         const sdh::RatchetGroup* groups, const int64_t* ts, int64_t seq_base,
-                                         int64_t seq_ref, const int32_t* out_rank, int n_streams, int n_blocks,
-                                         sdh::MatchTable T, int64_t row0, int64_t word0, hipStream_t s);
-extern "C" hipError_t sdh_append_chain(const int64_t* src, const int64_t* seg_off, const int64_t* seg_count,
-                                       const int64_t* dst_off, int rec_words, int n_items, const int32_t* qinfo,
-                                       int64_t seq_ref, const int32_t* out_rank, int n_streams, sdh::MatchTable T,
-                                       int64_t row0, int64_t word0, hipStream_t s);
-extern "C" size_t sdh_gen_words_temp_bytes(int64_t n_rec);
-extern "C" size_t sdh_sorted_batch_bytes(const sdh::StreamBatch* b);
-extern "C" hipError_t sdh_sort_batch(const sdh::StreamBatch* b, const int32_t* idx, uint8_t* buf, sdh::StreamBatch* o,
-                                     hipStream_t s);
-extern "C" hipError_t sdh_gen_words(const int64_t* out, const int64_t* rec_off, int64_t n_rec, int64_t* tw, void* temp,
-                                    size_t temp_bytes, unsigned long long* n_wide, hipStream_t s);
-extern "C" size_t sdh_ex_temp_bytes(int64_t n);
-extern "C" hipError_t sdh_ex_chain_words(sdh::MatchTable T, const int32_t* perm, int64_t n, int64_t* cw, void* temp,
-                                         size_t temp_bytes, hipStream_t s);
-extern "C" hipError_t sdh_ex_rows(sdh::MatchTable T, const int32_t* perm, int64_t n, int width, int64_t seq_ref,
-                                  const int64_t* coff, int32_t* rows, int32_t* chain, int64_t* okey, int64_t* otb,
-                                  int32_t* err, hipStream_t s);
-extern "C" hipError_t sdh_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t s);
-extern "C" hipError_t sdh_append_gen(const int64_t* out, const int64_t* rec_off, int64_t n_rec, int64_t seq_ref,
-                                     const int32_t* out_rank, const int32_t* fan_rank, int n_streams, sdh::MatchTable T,
-                                     int64_t row0, int64_t word0, const int64_t* woff, const int64_t* bts,
-                                     int64_t seq_base, int bstream, const int64_t* const* qkeys, hipStream_t s);
-extern "C" hipError_t sdh_new_keys(const uint32_t* uniq, const int32_t* nruns, int64_t max_runs, const int32_t* off,
-                                   const int32_t* idx_s, const int64_t* key_of_id, int64_t old_n, int64_t new_n,
-                                   int64_t* out, hipStream_t s);
-extern "C" size_t sdh_poll_temp_bytes(int64_t n);
-extern "C" hipError_t sdh_gen_journal(int32_t* a32, int64_t* a64, int64_t B32, int64_t B64, int mode,
-                                       const int32_t* glist, const uint32_t* seg_kid, int groups, int64_t slots,
-                                       int32_t* j32, int64_t* j64, int64_t* jidx, int restore, hipStream_t s);
-extern "C" size_t sdh_place_temp_bytes(int64_t cells);
-extern "C" size_t sdh_prefix_max_temp_bytes(int64_t n);
-extern "C" hipError_t sdh_prefix_max(const int64_t* ts, int64_t n, int64_t* pm, int32_t* unordered, void* temp,
-                                     size_t temp_bytes, hipStream_t s);
-extern "C" hipError_t sdh_key_segments(const uint32_t* uniq, const int32_t* nruns, int64_t max_runs, int64_t n_keys,
-                                       int32_t* kseg, hipStream_t s);
-extern "C" hipError_t sdh_digest_compact(const int32_t* crow, int width, int64_t row0, int64_t n, int64_t seq_ref,
-                                         unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_place_scan(int32_t* cnt, int64_t cells, void* temp, size_t temp_bytes, hipStream_t s);
-extern "C" hipError_t sdh_merge_keys_table(sdh::MatchTable T, const int32_t* perm, int64_t n, int chunk_words,
-                                           int lo_words, int chunked, uint64_t* keys, hipStream_t s);
-extern "C" hipError_t sdh_merge_keys_placed(const int32_t* crow, int width, int64_t n, int64_t seq_ref,
-                                            const int32_t* out_rank, const int32_t* qinfo, int n_streams,
-                                            int chunk_words, int lo_words, uint64_t* keys, hipStream_t s);
-extern "C" hipError_t sdh_place_total(const int32_t* cnt, int64_t cells, unsigned long long* tot, hipStream_t s);
-extern "C" hipError_t sdh_compact_fill(const int32_t* crow, int width, int64_t rows, const int64_t* ts_log,
-                                       int64_t seq_ref, int64_t* oq, int64_t* okey, int64_t* ots, int64_t* oseq,
-                                       int64_t* otb, int64_t* ooff, int64_t* owords, hipStream_t s);
-extern "C" hipError_t sdh_placed_to_table(const int32_t* crow, int width, int64_t n, const int64_t* ts_log,
-                                          int64_t seq_ref, const int32_t* out_rank, const int32_t* qinfo,
-                                          int n_streams, sdh::MatchTable T, hipStream_t s);
-extern "C" hipError_t sdh_table_compact(sdh::MatchTable T, const int32_t* perm, int64_t n, int width, int64_t seq_ref,
-                                        int32_t* crow, int32_t* err, hipStream_t s);
-extern "C" hipError_t sdh_live_gen(const int32_t* a32, int64_t B32, int64_t blocks, int n_groups, int group_base,
-                                    const int32_t* lane_q, const int32_t* group_seq, const sdh::kg::GQuery* queries,
-                                    unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_live_seq(const int64_t* tail, int tail_len, int stream, const int32_t* groups, int n_groups,
-                                   const int32_t* lane_q, const int32_t* group_tmpl, const sdh::kg::GQuery* queries,
-                                   unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_live_part(const int64_t* st, const int32_t* cur, int64_t n_keys, int groups, int64_t blocks,
-                                    int64_t bw, unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_digest_ratchet(const int64_t* match, int blk_recs, int wide, const int32_t* blk_count,
-                                         const int32_t* blk_group, const int32_t* blk_side,
-                                         const sdh::RatchetGroup* groups, int64_t seq_base,
-                                         int n_blocks, unsigned long long* acc, hipStream_t s);
-extern "C" hipError_t sdh_launch_gate(int key_kind, int xmask, int full, int nf, int ng, int SC,
-                                      const sdh::RatchetLaunch* L, hipStream_t s);
-extern "C" int sdh_gate_occupancy(int nf, int ng);
-extern "C" size_t sdh_ratchet_compact_temp(int64_t n_blocks);
-extern "C" hipError_t sdh_ratchet_compact(const int64_t* match, int blk_recs, int wide, const int32_t* blk_count,
-                                          const int32_t* blk_group, const int32_t* blk_side,
-                                          const sdh::RatchetGroup* groups, int64_t seq_base, int n_blocks,
-                                          int64_t* row_off, void* temp, size_t temp_bytes, int width, int32_t* rows,
-                                          hipStream_t s);
-extern "C" hipError_t sdh_poll_sort(sdh::MatchTable T, int64_t n, int n_lo, int lo_bits, int hi_bits, int clo_bits,
-                                    uint64_t* kbuf, int32_t* pbuf, void* temp, size_t temp_bytes, int64_t* oq,
-                                    int64_t* okey, int64_t* ots, int64_t* oseq, int64_t* otb, int64_t* olen,
-                                    int64_t* ooff, int32_t** perm_out, int64_t* total_words, hipStream_t s);
-extern "C" hipError_t sdh_chunk_keys(sdh::MatchTable T, int64_t r0, int64_t r1, int chunk, int64_t cseq,
-                                     int64_t first_seq, int stream, int n_streams, const int32_t* major,
-                                     const int32_t* minor, const int32_t* qslot, const int32_t* runs,
-                                     int64_t n_events, hipStream_t s);
-extern "C" hipError_t sdh_poll_words(sdh::MatchTable T, const int32_t* perm, int64_t n, const int64_t* ooff,
-                                     int64_t* owords, hipStream_t s);
-
-using namespace sdh;
-
-namespace {
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-std::string fmt(const char* f, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, f);
-  vsnprintf(buf, sizeof buf, f, ap);
-  va_end(ap);
-  return buf;
-}
-
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) throw Error(SDH_E_DEVICE, fmt("%s: %s", #x, hipGetErrorString(e_))); \
-  } while (0)
-
-// ------------------------------------------------------------------------------------------
-// IR reader (format: siddhi_amd/ir.py)
-// ------------------------------------------------------------------------------------------
-enum { OP_CONST = 1, OP_ATTR, OP_IS_NULL, OP_STREAM_IS_NULL, OP_CMP, OP_AND, OP_OR, OP_NOT, OP_ARITH };
-enum { K_STREAM = 0, K_COUNT, K_LOGICAL };
-enum { Q_PATTERN = 0, Q_SEQUENCE };
-
-struct Insn {
-  int op, lt, rt, res;
-  int64_t a, b, imm;
-};
-struct IState {
-  int kind, stream, is_start, min, max, ltype, partner, next_pre, next_every, within_every, callback,
-      this_last, has_selector;
-  int64_t waiting;  // absent states: the 'for' time (ms), else -1
-  std::vector<std::vector<Insn>> filters;
-};
-struct IQuery {
-  int type, partition;
-  int64_t within;
-  std::vector<IState> st;
-};
-struct IProgram {
-  std::vector<std::vector<int>> stream_types;
-  std::vector<IQuery> q;
-};
-
-struct WordReader {
-  const int64_t* w;
-  size_t n, i = 0;
-  int64_t next() {
-    if (i >= n) throw Error(SDH_E_INVALID, "IR blob truncated");
-    return w[i++];
-  }
-};
-
-std::vector<Insn> read_code(WordReader& r) {
-  std::vector<Insn> c((size_t)r.next());
-  for (auto& x : c) {
-    int64_t w0 = r.next();
-    x.op = (int)(w0 & 0xff);
-    x.lt = (int)((w0 >> 8) & 0xff);
-    x.rt = (int)((w0 >> 16) & 0xff);
-    x.res = (int)((w0 >> 24) & 0xff);
-    x.a = r.next();
-    x.b = r.next();
-    x.imm = r.next();
-  }
-  return c;
-}
-
-IProgram read_ir(const void* blob, size_t len) {
-  if (!blob || len < 16 || memcmp(blob, "SDHIR001", 8) != 0) throw Error(SDH_E_INVALID, "bad IR magic");
-  WordReader r{reinterpret_cast<const int64_t*>(static_cast<const char*>(blob) + 8), (len - 8) / 8};
-  IProgram p;
-  if (r.next() != 2) throw Error(SDH_E_INVALID, "unsupported IR version");
-  p.stream_types.resize((size_t)r.next());
-  for (auto& s : p.stream_types) {
-    s.resize((size_t)r.next());
-    for (auto& t : s) t = (int)r.next();
-  }
-  int64_t ns = r.next();
-  for (int64_t k = 0; k < ns; ++k) {
-    int64_t nb = r.next();
-    for (int64_t j = 0; j < (nb + 7) / 8; ++j) r.next();
-  }
-  p.q.resize((size_t)r.next());
-  for (auto& q : p.q) {
-    q.type = (int)r.next();
-    q.within = r.next();
-    q.st.resize((size_t)r.next());
-    q.partition = (int)r.next();
-    r.next();
-    for (auto& s : q.st) {
-      s.kind = (int)r.next(); s.stream = (int)r.next(); s.is_start = (int)r.next();
-      s.min = (int)r.next(); s.max = (int)r.next(); s.ltype = (int)r.next();
-      s.partner = (int)r.next(); s.next_pre = (int)r.next(); s.next_every = (int)r.next();
-      s.within_every = (int)r.next(); s.callback = (int)r.next(); s.this_last = (int)r.next();
-      s.has_selector = (int)r.next();
-      s.waiting = r.next();
-      s.filters.resize((size_t)r.next());
-      for (auto& f : s.filters) f = read_code(r);
-    }
-    int64_t n = r.next();
-    for (int64_t k = 0; k < n; ++k) r.next();           // start ids
-    n = r.next();
-    for (int64_t k = 0; k < n; ++k) {                    // receivers
-      r.next(); r.next();
-      int64_t np = r.next();
-      for (int64_t j = 0; j < np; ++j) r.next();
-    }
-    n = r.next();
-    for (int64_t k = 0; k < n * 4; ++k) r.next();        // runtime tree
-    n = r.next();
-    for (int64_t k = 0; k < n; ++k) read_code(r);        // selector outputs (host-side projection)
-  }
-  return p;  // partitions follow; partitioned queries are rejected by the lowering below
-}
-
-// ------------------------------------------------------------------------------------------
-// lowering: IR query -> ChainQuery (predicate atoms + captures)
-// ------------------------------------------------------------------------------------------
-// Compare domain of a typed compare (restates ExpressionParser.java:539-1220 + compare/**):
-// ordering compares promote like Java binary numeric promotion; ==/!= of Long x Float compare in
-// double (EqualCompareConditionExpressionExecutorLongFloat.java:36, ...FloatLong.java:37).
-int domain_of(int lt, int rt, int op) {
-  if (lt == T_STRING || lt == T_BOOL) return D_RAW;
-  if (lt == T_DOUBLE || rt == T_DOUBLE) return D_F64;
-  if (lt == T_FLOAT || rt == T_FLOAT) {
-    if ((op == CMP_EQ || op == CMP_NE) && (lt == T_LONG || rt == T_LONG)) return D_F64;
-    return D_F32;
-  }
-  if (lt == T_LONG || rt == T_LONG) return D_I64;
-  return D_I32;
-}
-
-// conversion of an operand of attribute type t into the key of domain d (enum Conv)
-int conv_of(int t, int d) {
-  switch (d) {
-    case D_I32:
-    case D_I64: return t == T_INT ? CV_I64_INT : CV_I64_LONG;
-    case D_F32: return t == T_INT ? CV_F32_INT : t == T_LONG ? CV_F32_LONG : CV_F64_FLOAT;  // float->double is exact
-    case D_F64:
-      return t == T_INT ? CV_F64_INT : t == T_LONG ? CV_F64_LONG : t == T_FLOAT ? CV_F64_FLOAT : CV_F64_DOUBLE;
-    default: return CV_RAW;
-  }
-}
-
-int64_t host_key(int64_t raw, int conv) {  // host twin of to_key() in nfa_chain.hip
-  auto dbits = [](double d) { int64_t b; memcpy(&b, &d, 8); return b; };
-  auto f_of = [](int64_t r) { uint32_t u = (uint32_t)r; float f; memcpy(&f, &u, 4); return f; };
-  switch (conv) {
-    case CV_I64_INT: return (int64_t)(int32_t)(uint32_t)raw;
-    case CV_I64_LONG: return raw;
-    case CV_F32_INT: return dbits((double)(float)(int32_t)(uint32_t)raw);
-    case CV_F32_LONG: return dbits((double)(float)raw);
-    case CV_F32_FLOAT:
-    case CV_F64_FLOAT: return dbits((double)f_of(raw));
-    case CV_F64_INT: return dbits((double)(int32_t)(uint32_t)raw);
-    case CV_F64_LONG: return dbits((double)raw);
-    default: return raw;
-  }
-}
-
-int mask_of(int op) {
-  switch (op) {
-    case CMP_EQ: return CM_EQ;
-    case CMP_NE: return CM_EQ | CM_NOT;
-    case CMP_GT: return CM_GT;
-    case CMP_GE: return CM_GT | CM_EQ;
-    case CMP_LT: return CM_LT;
-    default: return CM_LT | CM_EQ;
-  }
-}
-
-struct Node {
-  int kind;  // 0 leaf operand, 1 cmp, 2 and, 3 other
-  Insn ins;
-  int l = -1, r = -1;
-};
-
-struct Lowered {
-  bool ok = false;
-  std::string why;
-  ChainQuery cq{};
-  std::vector<int> streams;
-};
-
-Lowered lower_query(const IProgram& P, int qi) {
-  Lowered L;
-  const IQuery& q = P.q[qi];
-  const int n = (int)q.st.size();
-  auto fail = [&](const std::string& w) { L.ok = false; L.why = fmt("query %d: %s", qi, w.c_str()); return L; };
-  if (q.partition >= 0) return fail("partitioned queries are not on the GPU path yet");
-  if (q.type != Q_PATTERN) return fail("sequences are not on the GPU path yet");
-  if (n < 1 || n > MAXS) return fail(fmt("%d states (chain kernel supports 1..%d)", n, MAXS));
-  ChainQuery& c = L.cq;
-  c.qid = qi;
-  c.n_states = n;
-  c.within = q.within;
-  for (int s = 0; s < n; ++s) {
-    const IState& st = q.st[s];
-    if (st.kind != K_STREAM) return fail("count/logical states are not on the GPU path yet");
-    if (st.is_start != (s == 0)) return fail("not a linear chain");
-    if (st.next_pre != (s + 1 < n ? s + 1 : -1)) return fail("not a linear chain");
-    if (s > 0 && st.next_every != -1) return fail("`every` inside the chain is not on the GPU path yet");
-    if (s == 0 && st.next_every != -1 && st.next_every != 0) return fail("every scope");
-    if (s > 0 && st.within_every != -1) return fail("within-every re-arm");
-    if (st.callback != -1) return fail("count callback");
-    if (st.has_selector != (s == n - 1)) return fail("selector placement");
-    c.state_stream[s] = st.stream;
-    if (std::find(L.streams.begin(), L.streams.end(), st.stream) == L.streams.end())
-      L.streams.push_back(st.stream);
-  }
-  c.every = q.st[0].next_every == 0;
-  for (int s = 0; s < n; ++s)
-    if ((int)P.stream_types[q.st[s].stream].size() > MAXATTR) return fail("too many attributes");
-  // a single input stream and `every` make event-chunk warm-up exact
-  c.chunkable = (L.streams.size() == 1) && c.every && q.within >= 0 && n >= 2;
-
-  int na = 0;
-  for (int s = 0; s < n; ++s) {
-    c.atom_begin[s] = na;
-    std::vector<Atom> const_atoms, x_atoms;
-    std::vector<int> x_cols;
-    for (const auto& code : q.st[s].filters) {
-      // postfix -> tree
-      std::vector<Node> nodes;
-      std::vector<int> stk;
-      for (const Insn& ins : code) {
-        Node nd;
-        nd.ins = ins;
-        if (ins.op == OP_CONST || ins.op == OP_ATTR) {
-          nd.kind = 0;
-        } else if (ins.op == OP_CMP || ins.op == OP_AND) {
-          nd.kind = ins.op == OP_CMP ? 1 : 2;
-          nd.r = stk.back(); stk.pop_back();
-          nd.l = stk.back(); stk.pop_back();
-        } else {
-          return fail("filter uses or/not/is-null/arithmetic (general predicate kernel pending)");
-        }
-        nodes.push_back(nd);
-        stk.push_back((int)nodes.size() - 1);
-      }
-      if (stk.size() != 1) return fail("malformed filter bytecode");
-      // flatten the conjunction into atoms
-      std::vector<int> todo{stk.back()};
-      std::vector<int> leaves;
-      while (!todo.empty()) {
-        int x = todo.back(); todo.pop_back();
-        if (nodes[x].kind == 2) { todo.push_back(nodes[x].r); todo.push_back(nodes[x].l); }
-        else leaves.push_back(x);
-      }
-      for (int x : leaves) {
-        Atom A{};
-        const Node& nd = nodes[x];
-        Insn li, ri;
-        int op;
-        if (nd.kind == 1) {
-          if (nodes[nd.l].kind != 0 || nodes[nd.r].kind != 0)
-            return fail("compare of computed values (general predicate kernel pending)");
-          li = nodes[nd.l].ins;
-          ri = nodes[nd.r].ins;
-          op = (int)nd.ins.imm;
-        } else if (nd.kind == 0 && nd.ins.res == T_BOOL) {
-          // bare bool operand as a filter: FilterProcessor drops null and false
-          li = nd.ins;
-          ri = Insn{OP_CONST, 0, 0, T_BOOL, 0, 0, 1};
-          op = CMP_EQ;
-        } else {
-          return fail("unsupported filter form");
-        }
-        const int dom = domain_of(li.res, ri.res, op);
-        A.mask = mask_of(op);
-        A.f64 = (dom == D_F32 || dom == D_F64) ? 1 : 0;
-        // operand -> (kind, index, const key); single-event slots resolve only chain index
-        // CURRENT (-1) and 0 (StateEvent.getStreamEvent:138-182), others read null
-        auto operand = [&](const Insn& in, int& k, int& idx, int64_t& cst) -> bool {
-          const int cv = conv_of(in.res, dom);
-          idx = 0;
-          cst = 0;
-          if (in.op == OP_CONST) { k = OPK_CONST; cst = host_key(in.imm, cv); return true; }
-          if (in.b != -1 && in.b != 0) { k = OPK_NULL; return true; }
-          if (in.a > s) return false;
-          const int st_stream = q.st[in.a].stream;
-          int col = -1;
-          for (int cc = 0; cc < c.n_col; ++cc)
-            if (c.col_attr[cc] == in.imm && c.col_conv[cc] == cv && c.col_stream[cc] == st_stream) col = cc;
-          if (col < 0) {
-            if (c.n_col >= MAXCOL) return false;
-            col = c.n_col++;
-            c.col_attr[col] = (int)in.imm;
-            c.col_conv[col] = cv;
-            c.col_stream[col] = st_stream;
-          }
-          if (in.a == s) { k = OPK_CUR; idx = col; return true; }
-          for (int cc = 0; cc < c.n_cap; ++cc)
-            if (c.cap_slot[cc] == in.a && c.cap_col[cc] == col) { k = OPK_CAP; idx = cc; return true; }
-          if (c.n_cap >= MAXCAP) return false;
-          c.cap_slot[c.n_cap] = (int)in.a;
-          c.cap_col[c.n_cap] = col;
-          k = OPK_CAP;
-          idx = c.n_cap++;
-          return true;
-        };
-        if (!operand(li, A.lk, A.li, A.lc) || !operand(ri, A.rk, A.ri, A.rc))
-          return fail("operand not addressable (too many columns / captures)");
-        if (A.lk == OPK_CAP || A.rk == OPK_CAP) {
-          x_atoms.push_back(A);
-          x_cols.push_back(A.lk == OPK_CUR ? A.li : A.rk == OPK_CUR ? A.ri : -1);
-        } else {
-          const_atoms.push_back(A);
-        }
-      }
-    }
-    // partial-independent atoms first (tile-vectorized), capture readers last (per partial)
-    if (na + (int)(const_atoms.size() + x_atoms.size()) > MAXATOM) return fail("too many predicate atoms");
-    if (c.n_xa + (int)x_atoms.size() > MAXXA) return fail("too many capture-reading predicate atoms");
-    for (const Atom& A : const_atoms) c.atoms[na++] = A;
-    c.xa_first[s] = c.n_xa;
-    c.xa_count[s] = (int)x_atoms.size();
-    for (size_t k = 0; k < x_atoms.size(); ++k) {
-      c.atoms[na] = x_atoms[k];
-      c.xa_atom[c.n_xa] = na;
-      c.xa_col[c.n_xa] = x_cols[k];
-      ++c.n_xa;
-      ++na;
-    }
-  }
-  c.atom_begin[n] = na;
-  for (int s = n + 1; s <= MAXS; ++s) c.atom_begin[s] = na;
-  L.ok = true;
-  return L;
-}
-
-int attr_width(int t) {
-  switch (t) {
-    case T_INT: case T_FLOAT: case T_STRING: return 4;
-    case T_BOOL: return 1;
-    default: return 8;
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// K_ratchet plan selection: 2-state `every e1=S[f0] -> e2=S[cur.a OP e1.a]`
-// ------------------------------------------------------------------------------------------
-struct RatchetPlan {
-  bool ok = false;
-  int stream = 0, key_attr = 0, key_conv = 0, key_kind = 0, xmask = 0;
-  std::vector<RatchetAtom> f0;
-  std::vector<int64_t> f0c;
-  // K_gate (nfa_gate.hip): e2's event-only conjuncts `cur.b OP const` (empty: plain K_ratchet)
-  std::vector<RatchetAtom> g;
-  std::vector<int64_t> gc;
-  int64_t within = -1;
-  // grouping signature: everything except the per-lane constants and `within`
-  std::vector<int64_t> sig() const {
-    std::vector<int64_t> v{stream, key_kind, key_attr, key_conv, xmask, within >= 0, (int64_t)f0.size(),
-                           (int64_t)g.size()};
-    for (const auto* atoms : {&f0, &g})
-      for (const auto& a : *atoms)
-        v.insert(v.end(), {a.attr, a.conv, a.cur_left, a.mask, a.f64, a.cur2, a.attr2, a.conv2});
-    return v;
-  }
-};
-
-// an event-only atom `cur OP const` / `const OP cur` (a start filter's or a gate's) as a RatchetAtom
-// and its constant; false for any other operand shape
-bool const_atom(const ChainQuery& c, const Atom& A, RatchetAtom& ra, int64_t& cst) {
-  ra = RatchetAtom{};
-  ra.mask = A.mask;
-  ra.f64 = A.f64;
-  if (A.lk == OPK_CUR && A.rk == OPK_CONST) {
-    ra.attr = c.col_attr[A.li]; ra.conv = c.col_conv[A.li]; ra.cur_left = 1; cst = A.rc;
-  } else if (A.lk == OPK_CONST && A.rk == OPK_CUR) {
-    ra.attr = c.col_attr[A.ri]; ra.conv = c.col_conv[A.ri]; ra.cur_left = 0; cst = A.lc;
-  } else {
-    return false;
-  }
-  return true;
-}
-
-RatchetPlan ratchet_plan(const ChainQuery& c) {
-  RatchetPlan r;
-  if (c.n_states != 2 || !c.every || c.state_stream[0] != c.state_stream[1]) return r;
-  if (c.n_cap != 1 || c.cap_slot[0] != 0) return r;
-  if (c.xa_count[1] != 1 || c.xa_count[0] != 0) return r;
-  const int x_at = c.xa_atom[c.xa_first[1]];
-  // state 1's other atoms: event-only constant compares gate it (K_gate); none for K_ratchet
-  for (int a = c.atom_begin[1]; a < c.atom_begin[2]; ++a) {
-    if (a == x_at) continue;
-    RatchetAtom ga;
-    int64_t cst = 0;
-    if (!const_atom(c, c.atoms[a], ga, cst) || r.g.size() >= (size_t)RMAXF0) return RatchetPlan();
-    r.g.push_back(ga);
-    r.gc.push_back(cst);
-  }
-  const Atom& X = c.atoms[x_at];
-  int mask = X.mask;
-  if (mask & CM_NOT) return r;
-  if (!(mask & (CM_LT | CM_GT)) || ((mask & CM_LT) && (mask & CM_GT))) return r;  // ordering only
-  int cur_col;
-  if (X.lk == OPK_CUR && X.rk == OPK_CAP) {
-    cur_col = X.li;
-  } else if (X.lk == OPK_CAP && X.rk == OPK_CUR) {
-    cur_col = X.ri;
-    const int lt = mask & CM_LT, gt = mask & CM_GT;
-    mask = (mask & CM_EQ) | (lt ? CM_GT : 0) | (gt ? CM_LT : 0);  // key OP cur == cur OP' key
-  } else {
-    return r;
-  }
-  if (c.cap_col[0] != cur_col) return r;  // key = e1 value of the same column and conversion
-  const int conv = c.col_conv[cur_col];
-  // both operands are the same column with the same conversion: a float column compared in
-  // binary64 orders exactly as in binary32, an int column as int32 (32-bit ring entries)
-  switch (conv) {
-    case CV_F32_INT: case CV_F32_LONG: case CV_F32_FLOAT: case CV_F64_FLOAT: r.key_kind = KK_F32; break;
-    case CV_I64_INT: case CV_F64_INT: r.key_kind = KK_I32; break;
-    case CV_I64_LONG: r.key_kind = KK_I64; break;
-    case CV_F64_LONG: case CV_F64_DOUBLE: r.key_kind = KK_F64; break;
-    default: return r;
-  }
-  if (r.key_kind < 0) return r;
-  if (!r.g.empty() && r.key_kind != KK_F32 && r.key_kind != KK_I32) return RatchetPlan();  // (K_gate: 32-bit keys)
-  const int na0 = c.atom_begin[1] - c.atom_begin[0];
-  if (na0 > RMAXF0) return r;
-  for (int a = c.atom_begin[0]; a < c.atom_begin[1]; ++a) {
-    const Atom& A = c.atoms[a];
-    RatchetAtom ra{};
-    ra.mask = A.mask;
-    ra.f64 = A.f64;
-    int64_t cst = 0;
-    if (A.lk == OPK_CUR && A.rk == OPK_CONST) {
-      ra.attr = c.col_attr[A.li]; ra.conv = c.col_conv[A.li]; ra.cur_left = 1; cst = A.rc;
-    } else if (A.lk == OPK_CONST && A.rk == OPK_CUR) {
-      ra.attr = c.col_attr[A.ri]; ra.conv = c.col_conv[A.ri]; ra.cur_left = 0; cst = A.lc;
-    } else if (A.lk == OPK_CUR && A.rk == OPK_CUR && r.g.empty()) {  // (K_gate: constant atoms only)
-      ra.attr = c.col_attr[A.li]; ra.conv = c.col_conv[A.li]; ra.cur_left = 1;
-      ra.cur2 = 1; ra.attr2 = c.col_attr[A.ri]; ra.conv2 = c.col_conv[A.ri];
-    } else {
-      return r;  // null operands / constant-only atoms: leave them to K_chain
-    }
-    r.f0.push_back(ra);
-    r.f0c.push_back(cst);
-  }
-  r.stream = c.state_stream[0];
-  r.key_attr = c.col_attr[cur_col];
-  r.key_conv = conv;
-  r.xmask = mask;
-  r.within = c.within;
-  r.ok = true;
-  return r;
-}
-
-// SDH_ALLOC_TRACE=1: one stderr line per device buffer (re)allocation (p99 push/poll latency hunts)
-inline void alloc_trace(const char* what, size_t bytes) {
-  const bool on = sdh::knob("SDH_ALLOC_TRACE") != nullptr;
-  if (on) fprintf(stderr, "[sdh] alloc %s %zu bytes\n", what, bytes);
-}
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  // grows by at least half its size (a buffer sized per push or per poll would otherwise be freed and
-  // allocated again whenever the count edges up: hipFree synchronises the device, a p99 spike)
-  // The first allocation takes an eighth more than asked: a buffer sized exactly by its first push
-  // or poll reallocated at the next one a few elements larger (C2's 64K-push leg: a 1.1-s poll, eight
-  // ~4-GB hipFree + hipMalloc pairs)
-  void ensure(size_t want) {
-    if (want <= n) return;
-    const size_t cap = std::max(want + want / 8, n + n / 2);
-    alloc_trace("ensure", cap * sizeof(T));
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
-    n = 0;
-    if (hipMalloc(&p, cap * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      HIPCHK(hipMalloc(&p, want * sizeof(T)));
-      n = want;
-      return;
-    }
-    n = cap;
-  }
-  // grow to at least `want` elements keeping the first `keep` (stream-ordered copy)
-  void grow_keep(size_t want, size_t keep, hipStream_t s) {
-    if (want <= n) return;
-    // (an eighth more on the first allocation, as ensure; and at least 1 MB: growing state tables of a
-    // few hundred KB doubled inside small pushes -- C2's 1-event pushes, a 1.1-ms p99)
-    size_t cap = std::max(std::max(want + want / 8, n * 2), ((size_t)1 << 20) / sizeof(T));
-    alloc_trace("grow_keep", cap * sizeof(T));
-    T* q = nullptr;
-    if (hipMalloc(&q, cap * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      cap = want;
-      if (hipMalloc(&q, cap * sizeof(T)) != hipSuccess)
-        throw Error(SDH_E_CAPACITY, fmt("device memory exhausted growing a %zu-byte buffer", cap * sizeof(T)));
-    }
-    if (p && keep) HIPCHK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (p) HIPCHK(hipFree(p));
-    p = q;
-    n = cap;
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-// host output buffer of a poll: pinned when the runtime grants it (faster D2H), else pageable
-template <class T>
-struct HostBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  bool pinned = false;
-  void ensure(size_t want) {
-    if (want <= n) return;
-    release();
-    const size_t cap = std::max(want + want / 8, n * 2);  // (an eighth of headroom, as DevBuf)
-    alloc_trace("host", cap * sizeof(T));
-    if (hipHostMalloc((void**)&p, cap * sizeof(T), hipHostMallocDefault) == hipSuccess) {
-      pinned = true;
-    } else {
-      (void)hipGetLastError();
-      p = (T*)malloc(cap * sizeof(T));
-      if (!p) throw Error(SDH_E_CAPACITY, "host memory exhausted for the poll output");
-      pinned = false;
-    }
-    n = cap;
-  }
-  void release() {
-    if (!p) return;
-    if (pinned) (void)hipHostFree(p);
-    else free(p);
-    p = nullptr;
-  }
-  ~HostBuf() { release(); }
-};
-
-
-}  // namespace
-
-struct sdh_engine {
-  sdh_config cfg{};
-  int dev = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  IProgram prog;
-  std::vector<Lowered> lq;           // local (this shard's) queries
-  int K = 1, pcap = 64, rec_words = 3;
-  DevBuf<ChainQuery> d_q;
-  DevBuf<InstHeader> d_hdr[2];
-  DevBuf<int64_t> d_part[2];
-  std::vector<int> cur;              // which buffer holds each local query's state
-  // batch staging for host-resident input
-  DevBuf<uint8_t> d_batch;           // a host batch's columns in HBM (stage_host_batch)
-  HostBuf<uint8_t> stage[2];         // pinned staging slots
-  hipEvent_t ev_stage[2] = {nullptr, nullptr}, ev_h0 = nullptr, ev_h1 = nullptr;
-  int stage_next = 0;
-  hipStream_t h2d = nullptr;         // side stream of host-to-device batch copies
-  std::vector<int64_t> prev_ts;      // per stream
-  int64_t seq = 0;
-  // last launch
-  DevBuf<WorkItem> d_work;
-  DevBuf<int64_t> d_seg_count, d_seg_off, d_dst_off, d_match;
-  DevBuf<int32_t> d_err;
-  std::vector<WorkItem> work;
-  std::vector<int64_t> seg_count;
-  int64_t device_matches = 0;        // K_chain matches of the last push
-  // device match table (matches.hip): every match since the last poll with its R18 sort keys
-  struct Table {
-    DevBuf<uint64_t> hi, lo[MAXLO];
-    DevBuf<int64_t> seq, q, key, ts, woff, wlen, words;
-    int64_t n = 0, nw = 0;           // rows / words used
-    int n_lo = 0;                    // tiebreak passes the rows need
-    bool placed = false;             // the rows are K_ratchet matches already in R18 order in po_*
-    // chunk delivery keys (nfa_types.h): allocated once a chunk push joins the window; rows
-    // [0, ck_n) have theirs, the rest are single-event rows filled at the poll
-    DevBuf<uint64_t> chi, clo;
-    bool chunked = false;
-    bool chunk_pushed = false;       // a chunk push joined the window (every rank alike: same pushes)
-    int64_t ck_n = 0;
-    int64_t max_run = 0;             // largest run start / key position a chunk row carries
-  } mt;
-  // the chunk push in progress (sdh_batch.chunk): its first event's seq, its length, and per
-  // partition keyed on its stream each event's same-key run start (ck_runs[slot][event])
-  struct Chunk {
-    bool active = false;
-    int64_t first_seq = 0, n = 0;
-    int stream = -1;
-  } ck;
-  DevBuf<int32_t> ck_runs, d_ck_major, d_ck_minor, d_ck_qslot;
-  std::vector<int32_t> ck_major, ck_minor;  // [query][stream] subscriber rank (+1), rank in partition
-  int64_t seq_ref = 0;               // global seq at the last poll (<= every trigger seq in mt)
-  DevBuf<int32_t> d_out_rank;        // [query][stream] R18 receiver rank
-  DevBuf<int32_t> d_qinfo;           // [query] (states, stream of the last state)
-  // poll scratch and outputs (device), host copies of the outputs
-  DevBuf<uint64_t> p_keys;
-  DevBuf<int32_t> p_perm;
-  DevBuf<uint8_t> p_temp;
-  DevBuf<int64_t> po_q, po_key, po_ts, po_seq, po_tb, po_len, po_off, po_words;
-  HostBuf<int64_t> ho_q, ho_key, ho_ts, ho_seq, ho_tb, ho_off, ho_words;
-  // compact rows (sdh_matches_compact): a placed window's rows live here (the ABI columns are
-  // filled from them at a full poll), with the window's event times ts_log[seq - seq_ref]; cw =
-  // 2 + the most states any query has
-  DevBuf<int32_t> pc_rows, pc_err;
-  DevBuf<int64_t> ts_log;
-  HostBuf<int32_t> hc_rows;
-  int cw = 4;
-  // ---- K_gen (general interpreter) ----
-  kg::LProgram lp;                   // full IR (receivers, runtime tree, partitions)
-  std::vector<int> out_rank;         // R18 rank per (query, stream)
-  std::vector<kg::GQuery> gq;
-  DevBuf<kg::GQuery> d_gq;
-  std::vector<int32_t> lane_q;       // [group][64]
-  DevBuf<int32_t> d_lane_q;
-  DevBuf<int64_t> d_lconst;          // [group][lc_slots][64] lane constants (kg::LaneConsts)
-  int lc_slots = kg::LC_FIRST;
-  std::vector<int32_t> group_tmpl;   // [group] shape template (a member query)
-  DevBuf<int32_t> d_group_tmpl;
-  std::vector<int32_t> group_seq;    // [group] window length S when the group runs on K_seq, else 0
-  std::map<int, hipFunction_t> seq_spec;  // K_seq shape template -> its shape-compiled kernel (spec.h)
-  std::vector<DevBuf<int32_t>> d_glists;  // [stream] unpartitioned groups: K_seq rows, then K_gen groups
-  std::vector<DevBuf<int64_t>> seq_tail;  // [stream] last SEQ_TMAX events (K_seq windows)
-  std::vector<int32_t> seq_tail_len;
-  int gB32 = 1, gB64 = 1;
-  int gHotS = 1, gHotNU = 1;  // K_gen LDS hot-word cache extents (max states / node-mask words)
-  kg::Sizing gsz;                    // K_gen pool sizing (grows on overflow: gen_relayout)
-  // absent states (kgen.h fire_timers): the runtime's start time and whether any query has them
-  bool started = false;
-  int64_t start_ts = 0;
-  bool has_absent = false;
-  bool has_fanout = false;           // a partition query reads a stream the partition does not key
-  DevBuf<int32_t> d_fan_rank;        // [query][stream] its rank within the partition (fan-out), -1
-  int64_t advance_to = INT64_MIN;    // set while a time advance runs (sdh_engine_advance_time)
-  std::vector<char> gq_arena;        // [gq] the query runs on K_gen (has an instance arena)
-  int64_t gen_regrows = 0;           // pool growths so far (sdh_stats)
-  struct GenSet {
-    int partition = -1;              // -1: the unpartitioned K_gen queries
-    int group_base = 0, n_groups = 0;
-    int64_t key_cap = 0;             // instance blocks = key_cap * n_groups (partitioned)
-    DevBuf<int32_t> a32;
-    DevBuf<int64_t> a64;
-    DevBuf<int32_t> s32;             // scratch arenas of event chunks 1.. (unpartitioned sets)
-    DevBuf<int64_t> s64;
-    // exact re-runs: the blocks the current pass modifies, as they were before it (gen_journal)
-    DevBuf<int32_t> j32;
-    DevBuf<int64_t> j64, jidx;
-    int64_t jn = 0;
-  };
-  std::vector<std::unique_ptr<GenSet>> gsets;
-  // per partition: PartitionRuntime's key -> instance map (dense key ids), shared by the
-  // partition's K_gen set and K_part sets (PartitionRuntime.java:257-306)
-  struct Route {
-    DevBuf<unsigned long long> tkey;
-    DevBuf<int32_t> tid, n_keys;
-    DevBuf<int64_t> key_of_id;
-    int64_t tmask = 0, max_keys = 0;
-    // fan-out partitions: keys in creation order (dense id, value), for the junction-map order
-    bool track = false;
-    int kkind = 0;                   // key values: 0 int / long, 1 bool, 2 string (dictionary ids),
-                                     // 3 float, 4 double (raw bits; NaN canonical)
-    int64_t nk_seen = 0;
-    std::vector<int64_t> korder_kid, korder_key;
-    DevBuf<int64_t> nk_tmp;
-    struct Fan {
-      int64_t n = -1;  // keys the positions cover
-      DevBuf<int32_t> pos;
-    };
-    std::map<int, Fan> fan;  // [stream] per-kid positions in that stream's junction map
-  };
-  std::vector<std::unique_ptr<Route>> routes;  // [partition] (null: no device set uses it)
-  // K_part (nfa_part.hip): one set per (partition, kind); state blocks (key, group) double-buffered
-  // per key: cur[kid] says which of st[0] / st[1] holds the key's current tables
-  struct PartSet {
-    int partition = -1, kind = 0;
-    int group_base = 0, n_groups = 0;
-    int cap = 8, ew = 3, sA = 1, sB = 2, cmax = 0, n_e1 = 0, n_first = 0, n_last = 0;
-    int64_t key_cap = 0;
-    bool ran = false;                // launched in the current pass
-    DevBuf<int64_t> st;              // [2][key_cap * n_groups][PK_HDR + cap * ew][64]
-    DevBuf<int32_t> cur, nxt;        // [key_cap]
-    int64_t bw() const { return PK_HDR + (int64_t)cap * ew; }
-    std::map<int, hipFunction_t> spec;  // shape template -> shape-compiled kernel (spec.h)
-  };
-  std::vector<std::unique_ptr<PartSet>> psets;
-  // K_slab (nfa_slab.hip): one set per partition; its queries' partials as sparse entries, one block
-  // per (key, group) in nsub sub-rings of a slab, found through the directory [key][group]
-  struct SlabSet {
-    int partition = -1;
-    int group_base = 0, n_groups = 0;
-    int64_t key_cap = 0;
-    std::vector<slab::Shape> shapes;
-    std::vector<int32_t> group_shape, group_ew;
-    DevBuf<slab::Shape> d_shapes;
-    DevBuf<int32_t> d_group_shape, d_group_ew;
-    std::vector<std::vector<int32_t>> glist;  // [stream] set groups reading it
-    std::vector<DevBuf<int32_t>> d_glist;
-    DevBuf<uint64_t> dir;                     // [key_cap * n_groups]
-    int nsub = 256;                           // sub-rings (separate buffers: they grow one at a time)
-    std::vector<uint32_t*> ring;
-    std::vector<int64_t> cap;                 // words per ring
-    DevBuf<uint32_t*> d_ring;
-    DevBuf<int64_t> d_cap;
-    DevBuf<unsigned long long> head, tail, head_bak;
-    std::vector<unsigned long long> h_head, h_tail, h_push0;  // h_push0: heads before the last push
-    // Ring buffers are carved from an arena of large chunks that are never returned while the engine
-    // lives: a ring that grows takes a new range and gives its old one back to the free list (adjacent
-    // free ranges merge), so growing costs no driver allocation once the arena holds enough. (A
-    // hipMalloc of GBs stalls for seconds from time to time on this driver, whether or not memory
-    // was freed; tools/alloc_probe.py.) sdh_engine_reserve sizes the arena up front.
-    struct Chunk {
-      uint8_t* base;
-      size_t bytes;
-      std::map<size_t, size_t> free;  // offset -> length
-    };
-    std::vector<Chunk> chunks;
-    size_t arena_bytes = 0;
-    bool add_chunk(size_t bytes) {
-      void* p = nullptr;
-      alloc_trace("slab_chunk", bytes);
-      if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-      }
-      chunks.push_back(Chunk{(uint8_t*)p, bytes, {}});
-      chunks.back().free[0] = bytes;
-      arena_bytes += bytes;
-      return true;
-    }
-    uint32_t* take(size_t bytes) {
-      for (auto& c : chunks)
-        for (auto it = c.free.begin(); it != c.free.end(); ++it) {
-          if (it->second < bytes) continue;
-          const size_t off = it->first, len = it->second;
-          c.free.erase(it);
-          if (len > bytes) c.free[off + bytes] = len - bytes;
-          return (uint32_t*)(c.base + off);
-        }
-      return nullptr;
-    }
-    uint32_t* alloc_ring(int64_t words) {
-      const size_t bytes = ((size_t)words * 4 + 4095) & ~(size_t)4095;
-      if (uint32_t* p = take(bytes)) return p;
-      // a new chunk: as large as the arena so far (the chunks double), or what the device still has
-      size_t want = std::max(bytes, std::max(arena_bytes, (size_t)1 << 30));
-      for (;;) {
-        if (add_chunk(want)) return take(bytes);
-        if (want == bytes) return nullptr;
-        want = std::max(bytes, want / 2);
-      }
-    }
-    void free_ring(uint32_t* p, int64_t words) {
-      if (!p) return;
-      const size_t bytes = ((size_t)words * 4 + 4095) & ~(size_t)4095;
-      for (auto& c : chunks) {
-        if ((uint8_t*)p < c.base || (uint8_t*)p >= c.base + c.bytes) continue;
-        size_t off = (size_t)((uint8_t*)p - c.base), len = bytes;
-        auto nx = c.free.lower_bound(off);
-        if (nx != c.free.end() && nx->first == off + len) {
-          len += nx->second;
-          nx = c.free.erase(nx);
-        }
-        if (nx != c.free.begin()) {
-          auto pv = std::prev(nx);
-          if (pv->first + pv->second == off) {
-            off = pv->first;
-            len += pv->second;
-            c.free.erase(pv);
-          }
-        }
-        c.free[off] = len;
-        return;
-      }
-    }
-    ~SlabSet() {
-      for (auto& c : chunks) (void)hipFree(c.base);
-    }
-    DevBuf<long long> live, live_bak;
-    DevBuf<unsigned long long> traffic;       // block bytes read + written by the last launch
-    DevBuf<uint64_t> journal, journal_idx;
-    int64_t items = 0;                        // items of this pass's launch (0: not launched)
-    int lds_words = 4096;                     // LDS rows (uint32 words) of the large tier
-    DevBuf<int32_t> defer, defer_n;           // items deferred to the large tier (nfa_slab.hip)
-    int64_t deferred = 0;
-    int64_t cleanings = 0, growths = 0;
-  };
-  std::vector<std::unique_ptr<SlabSet>> ssets;
-  DevBuf<int32_t> d_serr;            // per K_slab set: [0] LDS capacity, [1] slab space, [2] output overflow
-  int64_t slab_items = 0;            // K_slab work items of the last push
-  std::vector<int64_t> part_kept;    // per partition: events of the last push routed to a key here
-  DevBuf<int32_t> d_perr;            // per K_part set: [0] entry capacity, [2] output overflow
-  DevBuf<unsigned long long> d_pprof;  // SDH_PART_PROF measurement builds: phase clocks
-  DevBuf<int64_t> r_key;
-  DevBuf<int64_t> t_pm;              // indexed timer sweep: the batch's timestamp prefix max
-  DevBuf<int32_t> t_kseg, t_flag;    // per known key its routed segment; ts-order flag
-  DevBuf<uint8_t> t_temp;
-  DevBuf<uint32_t> r_kid, r_kid_s, r_uniq;
-  DevBuf<int32_t> r_idx, r_idx_s, r_cnt, r_off, r_nruns;
-  DevBuf<uint8_t> r_temp;
-  DevBuf<int64_t> g_out;
-  int64_t g_out_cap = 0;             // K_gen match record words per push
-  DevBuf<unsigned long long> g_out_next;
-  DevBuf<unsigned long long> g_nrec;
-  DevBuf<int64_t> g_rec_off;         // word offset of each K_gen / K_seq / K_part record of the last push
-  DevBuf<int64_t> g_tw;              // their table words, scanned (append_gen)
-  DevBuf<uint8_t> g_twtemp;
-  DevBuf<unsigned long long> g_nwide;  // K_gen-format (not narrow) records of the last append
-  // sdh_engine_poll_compact_ex outputs
-  DevBuf<int64_t> px_cw, px_key, px_tb;
-  DevBuf<int32_t> px_chain;
-  DevBuf<uint8_t> px_temp;
-  HostBuf<int64_t> hx_key, hx_tb;
-  HostBuf<int32_t> hx_chain;
-  DevBuf<const int64_t*> d_qkeys;    // [query] its partition's key table (narrow K_part records)
-  DevBuf<uint8_t> sb_buf;            // a batch in key order (K_part reads; sdh_sort_batch)
-  DevBuf<unsigned long long> g_rec_next;
-  int64_t g_dev_matches = 0;         // K_gen / K_seq matches of the last push
-  int64_t g_used = 0;                // words of the last push's records in g_out
-  bool g_journal = false;            // the current K_gen pass journals the blocks it modifies
-  // ---- K_ratchet groups ----
-  std::vector<RatchetGroup> rg;
-  std::vector<int> rcur;             // per group: buffer holding its deques
-  DevBuf<RatchetGroup> d_rg;
-  DevBuf<RatchetState> d_rst[2];
-  DevBuf<int64_t> d_rts[2], d_rsq[2], d_rky[2];
-  DevBuf<RatchetItem> d_ritems;
-  std::vector<RatchetItem> ritems;
-  DevBuf<int64_t> d_rmatch;
-  DevBuf<int32_t> d_blk_count, d_blk_next, d_blk_group;
-  DevBuf<int32_t> d_blk_side;            // K_ratchet rec4 blocks: side entries (-1: an 8- / 16-B block)
-  // shared-pops form (nfa_ratchet_shared.hip): the pre-pass's tree, N(i) keys / values (unsorted and
-  // sorted), pairs, counts, sort scratch, and the groups' carried matches
-  DevBuf<float> d_shtree;
-  DevBuf<uint32_t> d_shkv, d_shcnt;
-  DevBuf<sdh::SharedPair> d_shpairs;
-  DevBuf<uint8_t> d_shtemp;
-  DevBuf<uint2> d_shcm;
-  DevBuf<int32_t> d_shcmn;
-  int64_t r_launches = 0;                // K_ratchet steps so far (SDH_RATCHET_SHARED_ALT)
-  int64_t r_shared_pushes = 0;           // pushes whose records the shared-pops form wrote
-  int64_t r_rec4_reruns = 0;             // pushes re-run with 8-B records (a rec4 distance reached 2^26)
-  DevBuf<unsigned long long> d_rtotal;  // device records: [0] entries, [2] bytes written
-  int r_wide = 0;
-  int64_t r_blocks = 0;              // capacity in blocks
-  int r_blk_recs = 8192;
-  int r_blocks_used = 0;             // of the last launch
-  int64_t r_blk_taken = 0;           // blocks the last launch took
-  double r_rec_bytes = 0;            // device records: bytes the last launch wrote (entries + side entries)
-  int r_rec4 = 0;                    // device records: the last launch wrote rec4 blocks (SIM launches)
-  DevBuf<int32_t> d_rlane_q;         // [group][64] query of each K_ratchet lane (-1 idle; sdh_records)
-  DevBuf<int64_t> d_rrow_off;        // sdh_engine_records_compact: per-block row offsets
-  DevBuf<uint8_t> d_rrow_tmp;
-  bool dev_polled = false;           // the last push's device records were handed out
-  int64_t last_n = 0, last_seq_base = 0;  // the last push's events and first seq
-  // direct R18 placement (nfa_ratchet.hip PM): the (event, group cell) match counts, scanned
-  DevBuf<int32_t> p_cnt;
-  std::vector<int> place_cells;     // [stream] K_ratchet groups reading it (0: not placeable)
-  // string dictionary ids -> (String.hashCode, UTF-16 length) of their text (sdh_engine_set_strings):
-  // the fan-out order of partitions keyed by a string attribute
-  std::unordered_map<int32_t, std::pair<int32_t, int64_t>> str_info;
-  bool r_placing = false;            // the last K_ratchet launch placed its matches (compact rows)
-  int64_t r_place_row0 = 0;          //   from this row of pc_rows
-  DevBuf<uint8_t> p_ptemp;
-  int64_t r_seq_base = 0;            // seq of the last launch's first event
-  std::vector<int32_t> r_blk_count;
-  int slab_lds_small = 1024;          // K_slab small-tier LDS rows (SDH_SLAB_LDS_SMALL)
-  int xcd = 0;                       // per-XCD item ranges in the K_gen / K_seq / K_part / K_slab launches
-                                     // (dev::grid_item; SDH_XCD=1: measured neutral)
-  int rML = 8;                       // LDS ring entries per lane (power of two)
-  double r_waves = 0;                // resident-wave target per launch (0: CUs x occupancy)
-  int n_cu = 256;
-  std::vector<std::array<int, 4>> r_sum_specs;  // tile-summary rows: (stream, attr, conv, key kind)
-  DevBuf<uint64_t> d_tsmax, d_tsmin;
-  DevBuf<uint8_t> d_tshas;
-  int rSC = 256;                     // global spill ring entries per lane (power of two)
-  int64_t rsmax = RSMAX;             // persisted deque entries per lane (grows with rSC)
-  DevBuf<uint4> d_rspillA;
-  DevBuf<int64_t> d_rlts;
-  DevBuf<uint32_t> d_rspillB;
-  std::vector<char> r_full_expiry;   // per stream: timestamps were seen out of order
-  int64_t r_matches = 0;
-  double r_kernel_ms = 0, r_kernel_bytes = 0;
-  sdh_stats stats{};
-  std::string err;
-  std::string broken;                // set when a failed push left the state undefined
-  std::vector<std::pair<std::string, std::string>> knobs;  // sdh_config.debug (knobs.h)
-  // ---- multi-GPU exchange (comm.h; sdh_engine_push_bcast / sdh_engine_gather) ----
-  sdh_comm* comm = nullptr;          // not owned
-  DevBuf<uint8_t> x_batch;           // a broadcast batch received from the root
-  DevBuf<uint64_t> x_keys;           // this rank's merge keys, one run
-  // rank 0: every rank's run concatenated, and the merged output
-  DevBuf<int64_t> xg_q, xg_key, xg_ts, xg_seq, xg_tb, xg_off, xg_words;
-  DevBuf<uint64_t> xg_keys;
-  DevBuf<int64_t> go_q, go_key, go_ts, go_seq, go_tb, go_len, go_off, go_src, go_pos, go_words;
-  DevBuf<uint8_t> go_temp;
-};
 
 namespace {
 
@@ -1314,19 +261,6 @@ void check_fan_strings(const sdh_engine* e, int stream) {
   }
 }
 
-// A normal-mode push places its K_ratchet matches directly (nfa_ratchet.hip PM: COUNT per (event,
-// group) cell, scan, WRITE as compact rows after the window's rows) when they are its only matches
-// -- the chain and K_gen launches ran first and produced none, and the window holds no table rows
-// --, the stream's groups are rank-ordered (place_cells), the cells stay within 2^30, the seqs of
-// the window within 2^31 of seq_ref, and the launch runs without the full-expiry scan.
-bool ratchet_placeable(const sdh_engine* e, int stream, int64_t seq_base, int64_t n_events, bool full) {
-  const int nc = e->place_cells[(size_t)stream];
-  return nc > 0 && !(e->cfg.flags & SDH_FLAG_DEVICE_MATCHES) && !full && n_events > 0 && !e->ck.active &&
-         e->device_matches == 0 && e->g_dev_matches == 0 && (e->mt.n == 0 || e->mt.placed) &&
-         (double)n_events * nc < (double)(1 << 30) && seq_base + n_events - e->seq_ref < INT32_MAX &&
-         !sdh::knob("SDH_NO_PLACE");
-}
-
 // a placed push joins the window: its rows are already in pc_rows; the compact rows carry seqs
 // only, so the window keeps the pushed events' times (ts_log[seq - seq_ref])
 void place_commit(sdh_engine* e, const int64_t* ts_col, int64_t seq_base, int64_t n_events) {
@@ -1411,650 +345,6 @@ void d2h_sync(sdh_engine* e, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipStreamSynchronize(e->stream));
 }
 
-void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
-            const std::vector<int>& qs, bool allow_chunks, bool* unordered) {
-  const int64_t n = B.n;
-  // chunk planning: enough waves to fill 256 CUs, chunks >> the warm-up window
-  double ev_per_ms = 1.0;
-  if (n > 1) ev_per_ms = (double)n / (double)std::max<int64_t>(1, t01[1] - t01[0]);
-  const int64_t min_chunk = e->cfg.chunk_events > 0 ? e->cfg.chunk_events : 4096;
-  const double target_waves = 16384.0;
-  // every wave replays (warm-up) + emits about the same number of events, so the launch has no
-  // serial tail: wave length T >= 2x the largest warm-up and ~ total work / target_waves
-  double max_warm = 0;
-  for (int li : qs) {
-    const ChainQuery& c = e->lq[li].cq;
-    if (c.chunkable) max_warm = std::max(max_warm, (double)c.within * ev_per_ms + 64.0);
-  }
-  const double T = std::max({2.0 * max_warm, (double)n * qs.size() / target_waves, 2.0 * min_chunk});
-  e->work.clear();
-  int64_t seg = 0;
-  // queries grouped by state count (one kernel instantiation per group)
-  std::vector<int> order(qs);
-  std::stable_sort(order.begin(), order.end(),
-                   [&](int a, int b) { return e->lq[a].cq.n_states < e->lq[b].cq.n_states; });
-  for (int li : order) {
-    const ChainQuery& c = e->lq[li].cq;
-    int64_t C = 1;
-    if (allow_chunks && c.chunkable) {
-      const double warm = (double)c.within * ev_per_ms + 64.0;
-      const double emit_len = std::max((double)min_chunk, T - warm);
-      C = std::max<int64_t>(1, (int64_t)std::ceil((double)n / emit_len));
-    }
-    for (int64_t ch = 0; ch < C; ++ch) {
-      WorkItem w{};
-      w.q = li;
-      w.chunk = (int)ch;
-      w.n_chunks = (int)C;
-      w.inb = e->cur[li];
-      w.c0 = n * ch / C;
-      w.c1 = n * (ch + 1) / C;
-      w.seg_off = seg;
-      w.seg_cap = (w.c1 - w.c0) + e->pcap + 1;
-      seg += w.seg_cap;
-      e->work.push_back(w);
-    }
-  }
-  const int n_items = (int)e->work.size();
-  e->d_work.ensure(n_items);
-  e->d_seg_count.ensure(n_items);
-  e->d_match.ensure((size_t)seg * e->rec_words);
-  e->d_err.ensure(4);
-  HIPCHK(hipMemcpyAsync(e->d_work.p, e->work.data(), n_items * sizeof(WorkItem), hipMemcpyHostToDevice,
-                        e->stream));
-  HIPCHK(hipMemsetAsync(e->d_err.p, 0, 16, e->stream));
-  ChainLaunch L{};
-  L.queries = e->d_q.p;
-  L.work = e->d_work.p;
-  L.n_work = n_items;
-  L.pcap = e->pcap;
-  L.b = B;
-  for (int b = 0; b < 2; ++b) {
-    L.hdr[b] = e->d_hdr[b].p;
-    L.part[b] = e->d_part[b].p;
-  }
-  L.match = e->d_match.p;
-  L.rec_words = e->rec_words;
-  L.seg_count = e->d_seg_count.p;
-  L.err = e->d_err.p;
-  const size_t lds = 0;
-  HIPCHK(hipEventRecord(e->ev0, e->stream));
-  for (int i0 = 0; i0 < n_items;) {
-    const int S = e->lq[e->work[i0].q].cq.n_states;
-    int i1 = i0;
-    while (i1 < n_items && e->lq[e->work[i1].q].cq.n_states == S) ++i1;
-    ChainLaunch Ls = L;
-    Ls.work = e->d_work.p + i0;
-    Ls.seg_count = e->d_seg_count.p + i0;
-    Ls.n_work = i1 - i0;
-    HIPCHK(sdh_launch_chain(S, e->K, &Ls, (Ls.n_work + 3) / 4, lds, e->stream));
-    i0 = i1;
-  }
-  HIPCHK(hipEventRecord(e->ev1, e->stream));
-  int32_t errs[4];
-  e->seg_count.resize(n_items);
-  HIPCHK(hipMemcpyAsync(errs, e->d_err.p, 16, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(e->seg_count.data(), e->d_seg_count.p, n_items * 8, hipMemcpyDeviceToHost,
-                        e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  e->stats.last_kernel_ms = ms;
-  if (errs[0]) throw Error(SDH_E_CAPACITY, "partial-match table overflow: raise partials_per_inst");
-  if (errs[2]) throw Error(SDH_E_CAPACITY, "match segment overflow");
-  *unordered = errs[1] != 0;
-  // algorithmic bytes of this launch: every item streams its [w0, c1) events once
-  // (approximated by c1-c0 plus warm-up), reads and writes its partial table, writes its matches
-  int64_t ev_bytes = 8;
-  for (int a = 0; a < B.n_attr; ++a) ev_bytes += B.width[a];
-  double bytes = 0;
-  int64_t total_matches = 0;
-  for (int i = 0; i < n_items; ++i) {
-    const WorkItem& w = e->work[i];
-    const ChainQuery& c = e->lq[w.q].cq;
-    double warm = w.chunk > 0 ? std::min<double>((double)w.c0, (double)c.within * ev_per_ms) : 0.0;
-    bytes += ((double)(w.c1 - w.c0) + warm) * ev_bytes;
-    total_matches += e->seg_count[i];
-  }
-  bytes += (double)qs.size() * 2.0 * NF * e->pcap * 8;  // partial tables in + out
-  bytes += (double)total_matches * e->rec_words * 8;
-  e->stats.last_kernel_bytes = bytes;
-  e->device_matches = total_matches;
-}
-
-// ------------------------------------------------------------------------------------------
-// K_ratchet host side
-// ------------------------------------------------------------------------------------------
-int ratchet_sim(const sdh::RatchetGroup& g);
-
-void ratchet_build(sdh_engine* e, std::vector<std::pair<RatchetPlan, int>>& plans) {
-  // lanes: normal mode in receiver-rank order (a wave's lanes are then consecutive ranks, which the
-  // direct placement needs: place_cells); SDH_FLAG_DEVICE_MATCHES mode by `within`, so that similar
-  // warm-up windows share a wave (SDH_RATCHET_LANES=rank|within overrides)
-  const char* lo = sdh::knob("SDH_RATCHET_LANES");
-  const bool by_rank = lo ? strcmp(lo, "rank") == 0 : !(e->cfg.flags & SDH_FLAG_DEVICE_MATCHES);
-  const size_t ns = e->prog.stream_types.size();
-  auto rank = [&](const std::pair<RatchetPlan, int>& p) { return e->out_rank[(size_t)p.second * ns + p.first.stream]; };
-  std::stable_sort(plans.begin(), plans.end(), [&](const auto& a, const auto& b) {
-    const auto sa = a.first.sig(), sb = b.first.sig();
-    if (sa != sb) return sa < sb;
-    if (by_rank) return rank(a) < rank(b);
-    return a.first.within < b.first.within;
-  });
-  for (size_t i = 0; i < plans.size();) {
-    size_t j = i;
-    const auto sg = plans[i].first.sig();
-    while (j < plans.size() && j - i < 64 && plans[j].first.sig() == sg) ++j;
-    RatchetGroup g{};
-    const RatchetPlan& P = plans[i].first;
-    g.n_lanes = (int)(j - i);
-    g.stream = P.stream;
-    g.key_attr = P.key_attr;
-    g.key_conv = P.key_conv;
-    g.key_kind = P.key_kind;
-    g.xmask = P.xmask;
-    g.n_f0 = (int)P.f0.size();
-    for (int a = 0; a < g.n_f0; ++a) g.f0[a] = P.f0[a];
-    g.n_g = (int)P.g.size();
-    for (int a = 0; a < g.n_g; ++a) g.g[a] = P.g[a];
-    g.sim = g.n_g ? 0 : ratchet_sim(g);
-    g.wmax = -1;
-    for (int l = 0; l < 64; ++l) {
-      const size_t k = i + std::min<size_t>(l, j - i - 1);  // idle lanes mirror the last pattern
-      const RatchetPlan& Q = plans[k].first;
-      g.qid[l] = plans[k].second;
-      g.within[l] = Q.within < 0 ? INT64_MAX : Q.within;
-      if (l < g.n_lanes) g.wmax = std::max(g.wmax, Q.within);
-      for (int a = 0; a < g.n_f0; ++a) g.f0c[a][l] = Q.f0c[a];
-      for (int a = 0; a < g.n_g; ++a) g.gc[a][l] = Q.gc[a];
-    }
-    e->rg.push_back(g);
-    i = j;
-  }
-  // per-tile x summaries: one row per distinct (stream, key column, conversion, key kind)
-  e->r_sum_specs.clear();
-  for (auto& g : e->rg) {
-    const std::array<int, 4> spec{g.stream, g.key_attr, g.key_conv, g.key_kind};
-    int slot = -1;
-    for (size_t k = 0; k < e->r_sum_specs.size(); ++k)
-      if (e->r_sum_specs[k] == spec) slot = (int)k;
-    if (slot < 0) {
-      slot = (int)e->r_sum_specs.size();
-      e->r_sum_specs.push_back(spec);
-    }
-    g.sum_slot = slot;
-  }
-  const size_t ng = e->rg.size();
-  e->rcur.assign(ng, 0);
-  e->r_full_expiry.assign(e->prog.stream_types.size(), 0);
-  if (!ng) return;
-  e->d_rg.ensure(ng);
-  HIPCHK(hipMemcpy(e->d_rg.p, e->rg.data(), ng * sizeof(RatchetGroup), hipMemcpyHostToDevice));
-  for (int b = 0; b < 2; ++b) {
-    e->d_rst[b].ensure(ng);
-    HIPCHK(hipMemset(e->d_rst[b].p, 0, ng * sizeof(RatchetState)));
-    e->d_rts[b].ensure(ng * e->rsmax * WAVE);
-    e->d_rsq[b].ensure(ng * e->rsmax * WAVE);
-    e->d_rky[b].ensure(ng * e->rsmax * WAVE);
-  }
-  e->d_blk_next.ensure(4);
-}
-
-// persisted deques with room for `want` entries per lane: [g][rsmax][64] re-strided (both buffers)
-void ratchet_grow_rsmax(sdh_engine* e, int64_t want) {
-  if (want <= e->rsmax) return;
-  int64_t cap = e->rsmax;
-  while (cap < want) cap *= 2;
-  const size_t ng = e->rg.size(), ob = (size_t)e->rsmax * WAVE * 8, nb = (size_t)cap * WAVE * 8;
-  for (int b = 0; b < 2; ++b)
-    for (DevBuf<int64_t>* buf : {&e->d_rts[b], &e->d_rsq[b], &e->d_rky[b]}) {
-      DevBuf<int64_t> nw;
-      nw.ensure(ng * cap * WAVE);
-      HIPCHK(hipMemcpy2DAsync(nw.p, nb, buf->p, ob, ob, ng, hipMemcpyDeviceToDevice, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      std::swap(buf->p, nw.p);
-      std::swap(buf->n, nw.n);
-    }
-  e->rsmax = cap;
-}
-
-int64_t ratchet_count_matches(sdh_engine* e) {
-  int64_t n = 0;
-  for (int i = 0; i < e->r_blocks_used; ++i) n += e->r_blk_count[i];
-  return n;
-}
-
-// one NFA step of every ratchet group fed by `stream` over batch B (exact re-runs on overflow /
-// out-of-order timestamps: the groups' input deques are double-buffered and untouched until the
-// launch succeeds)
-// f0 atoms a K_ratchet launch variant must handle: the one-atom variant assumes a constant
-// interval, so a group with a two-column atom (`cur.a OP cur.b`) takes the general variant
-int ratchet_nf(const sdh::RatchetGroup& g) {
-  for (int a = 0; a < g.n_f0; ++a)
-    if (g.f0[a].cur2) return sdh::RMAXF0;
-  return g.n_f0;
-}
-
-// the SIM form (nfa_ratchet.hip): float keys from a float column, one start atom over that same
-// column compared in the float / double domain against a constant, without negation
-int ratchet_sim(const sdh::RatchetGroup& g) {
-  if (sdh::knob("SDH_RATCHET_NO_SIM")) return 0;
-  if (g.key_kind != sdh::KK_F32 || g.key_conv == sdh::CV_F32_INT || g.key_conv == sdh::CV_F32_LONG || g.n_f0 != 1)
-    return 0;
-  const sdh::RatchetAtom& A = g.f0[0];
-  return (A.attr == g.key_attr && !A.cur2 && A.f64 && (A.conv == sdh::CV_F32_FLOAT || A.conv == sdh::CV_F64_FLOAT) &&
-          !(A.mask & sdh::CM_NOT)) ? 1 : 0;
-}
-
-void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2]) {
-  e->r_placing = false;
-  e->r_blocks_used = 0;
-  e->r_matches = 0;
-  e->r_kernel_ms = 0;
-  e->r_kernel_bytes = 0;
-  e->r_rec_bytes = 0;
-  e->r_rec4 = 0;
-  ++e->r_launches;
-  std::vector<int> gs;
-  for (int g = 0; g < (int)e->rg.size(); ++g)
-    if (e->rg[g].stream == stream) gs.push_back(g);
-  if (gs.empty()) return;
-  const int64_t n = B.n;
-  int64_t lanes = 0;
-  for (int g : gs) lanes += e->rg[g].n_lanes;
-  const bool devrec = (e->cfg.flags & SDH_FLAG_DEVICE_MATCHES) != 0;
-  if (e->r_blocks == 0) {
-    // a first guess (at most 8 GiB of blocks): a push that needs more re-runs once with the count of
-    // blocks its waves asked for
-    int64_t want = e->cfg.match_capacity > 0 ? e->cfg.match_capacity : std::max<int64_t>(1 << 20, n * lanes * 3 / 4);
-    if (e->cfg.match_capacity <= 0) want = std::min<int64_t>(want, (int64_t)1 << 30);
-    e->r_blocks = (want + e->r_blk_recs - 1) / e->r_blk_recs;
-  }
-  e->d_rtotal.ensure(3);  // [0] device-record entries, [1] the placement total, [2] device-record bytes
-  bool no_place = false, no_rec4 = false;
-  for (int attempt = 0; attempt < 40; ++attempt) {
-    // out-of-order timestamps seen on this stream, timestamps so extreme that `ts0 + within`
-    // could wrap, or a batch spanning 2^31 - 2 ms or more (the lazy forms' 32-bit deadline domain,
-    // nfa_ratchet.hip rel_deadline): exact per-entry expiry scan, no chunking
-    const int64_t lim = (int64_t)1 << 61;
-    const bool full = e->r_full_expiry[stream] != 0 || t01[0] < -lim || t01[0] > lim || t01[1] < -lim ||
-                      t01[1] > lim || (B.prev_ts != INT64_MIN && (B.prev_ts < -lim || B.prev_ts > lim)) ||
-                      t01[1] - t01[0] > (int64_t)INT32_MAX - 2;
-    // ---- chunk planning: chunk c > 0 rebuilds its starting deques by a reverse scan of the
-    // `within` window (a few instructions per 64 events), so chunks can be short. Each launch
-    // (one key kind x orientation) gets one resident wave per slot of the chip -- CUs x the
-    // kernel's occupancy -- of at least min_chunk emitted events each ----
-    // (C2 expansion, 64K-event pushes, tools/sweep_minchunk.sh: 2,048 events per chunk at least
-    // 3.66 ms per push / 3.56 compact, 1,024 3.42 / 3.43, 512 3.43 / 3.48, 256 3.68 / 3.68)
-    const int64_t def_chunk = sdh::knob("SDH_RATCHET_MIN_CHUNK") ? atoll(sdh::knob("SDH_RATCHET_MIN_CHUNK")) : 1024;
-    const int64_t min_chunk = e->cfg.chunk_events > 0 ? e->cfg.chunk_events : def_chunk;
-    e->ritems.clear();
-    std::vector<int> order(gs);
-    // launches: one per (key kind, orientation, SIM form); SIM also needs the key column null-free
-    // in this batch
-    auto lsim = [&](int g) { return e->rg[g].sim && !B.nul[e->rg[g].key_attr] ? 1 : 0; };
-    auto lgate = [&](int g) { return e->rg[g].n_g > 0 ? 1 : 0; };  // K_gate groups (nfa_gate.hip)
-    // the shared-pops form (nfa_ratchet_shared.hip): SIM launches writing rec4 device
-    // records of a push large enough to repay the pre-pass. SDH_RATCHET_SHARED_MIN, C2 at 10K patterns
-    // in device-record mode, ms per push with the form on / off: 4,096 events 0.51 /
-    // 0.52, 16,384 0.67 / 0.60, 65,536 1.21 / 1.21, 262,144 2.68 / 3.38, 8M 61.7 / 85.7 -- the default
-    // lies between the tie and the first clear gain. SDH_RATCHET_NO_SHARED switches the form off;
-    // SDH_RATCHET_SHARED_ALT=k (tests) keeps it to every other K_ratchet step, the odd ones for k = 1
-    const bool rec4_ok = devrec && n <= ((int64_t)1 << 26) && !full && !no_rec4;
-    bool use_shared = rec4_ok && !sdh::knob("SDH_RATCHET_NO_SHARED");
-    if (use_shared) {
-      const char* mn = sdh::knob("SDH_RATCHET_SHARED_MIN");
-      use_shared = n >= std::max<int64_t>(1, mn ? atoll(mn) : 131072);
-      if (const char* alt = sdh::knob("SDH_RATCHET_SHARED_ALT")) use_shared = use_shared && (e->r_launches & 1) == (atoi(alt) & 1);
-    }
-    auto lshared = [&](int g) {
-      return use_shared && lsim(g) && !lgate(g) && B.width[e->rg[g].key_attr] == 4;
-    };
-    // (a shared-pops launch has one pre-pass, so it also holds one key column: eligibility is per group,
-    // and the shared groups' launches are cut by column and conversion as well)
-    auto lkey = [&](int g) {
-      const bool sh = lshared(g);
-      return std::make_tuple(lgate(g), e->rg[g].key_kind, e->rg[g].xmask, lsim(g), sh ? 1 : 0,
-                             sh ? e->rg[g].key_attr : -1, sh ? e->rg[g].key_conv : -1);
-    };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lkey(a) < lkey(b); });
-    for (size_t i0 = 0; i0 < order.size();) {
-      size_t i1 = i0;
-      int nf = 0;
-      while (i1 < order.size() && lkey(order[i1]) == lkey(order[i0])) nf = std::max(nf, ratchet_nf(e->rg[order[i1++]]));
-      // items per launch: 8 rounds of the chip's resident slots (CUs x occupancy). Short chunks
-      // balance the groups' uneven match density, and a chunk's reverse-scan warm-up is cheap (tile
-      // summaries). C2 at 10K patterns, tools/sweep_ratchet.sh (SDH_RATCHET_WAVES): 8,192 items
-      // 117.8 ms/step, 16,384 110.9, 32,768 103.3, 65,536 100.2, 131,072 100.8, 524,288 104.4
-      double slots = e->r_waves;
-      if (slots <= 0) {
-        const int occ = lshared(order[i0]) ? sdh_ratchet_shared_occupancy()
-                        : lgate(order[i0]) ? sdh_gate_occupancy(nf, nf)
-                                         : sdh_ratchet_occupancy(e->rg[order[i0]].key_kind, full, nf, e->rML, lsim(order[i0]));
-        // (the shared-pops form, whose items have no warm-up to repeat: 16 rounds. SDH_RATCHET_WAVES at
-        // C2's 8M-event step: 16,384 items 70.3 ms, 32,768 64.3, 8 rounds 61.7, 131,072 60.3, 262,144 61.2)
-        slots = (lshared(order[i0]) ? 16.0 : 8.0) * (double)e->n_cu * std::max(1, occ);
-      }
-      // chunks per chunkable group: as many as fit the item target (floor, not ceil: a partial
-      // extra round of items runs as a nearly idle tail -- C2 at 10K once had 8,321 items for 8,192
-      // slots, 128.7 ms/step, against 117.7 at 8,164), at least min_chunk events each. Groups
-      // without `within` cannot chunk (no reverse-scan window) and hold one item each.
-      int64_t n_chunkable = 0;
-      // (the shared-pops form's items need no warm-up: every group chunks, `within` or not)
-      const bool shared = lshared(order[i0]);
-      for (size_t i = i0; i < i1; ++i) n_chunkable += (shared || (!full && e->rg[order[i]].wmax >= 0)) ? 1 : 0;
-      const int64_t free_slots = std::max<int64_t>(1, (int64_t)slots - ((int64_t)(i1 - i0) - n_chunkable));
-      const int64_t c_fit = n_chunkable > 0 ? std::max<int64_t>(1, free_slots / n_chunkable) : 1;
-      const int64_t c_min = std::max<int64_t>(1, n / std::max<int64_t>(1, min_chunk));
-      for (size_t i = i0; i < i1; ++i) {
-        const int g = order[i];
-        const RatchetGroup& G = e->rg[g];
-        int64_t C = 1;
-        if (shared) {
-          C = std::min(c_fit, c_min);
-        } else if (!full && G.wmax >= 0) {
-          C = std::min(c_fit, c_min);
-          // a chunk's warm-up walks its `within` window back from its first event: tiles whose best
-          // key is dominated by the later ones are skipped on their summary, but flat or rising key
-          // runs are walked event by event. Chunks x window events <= max(16 x the batch, 2^24)
-          // bounds that worst case (a 67M-event window spanning the batch: 16 chunks) and binds
-          // nowhere near C2's windows (1-60 s, up to 60K events, in 8M- or 64K-event pushes)
-          const double span = (double)std::max<int64_t>(1, t01[1] - t01[0]);
-          const double win_ev = std::min((double)n, (double)G.wmax * (double)n / span);
-          const double budget = std::max(16.0 * (double)n, 16777216.0);
-          C = std::min<int64_t>(C, std::max<int64_t>(1, (int64_t)(budget / std::max(1.0, win_ev))));
-        }
-        for (int64_t ch = 0; ch < C; ++ch) {
-          RatchetItem it{};
-          it.g = g;
-          it.chunk = (int)ch;
-          it.n_chunks = (int)C;
-          it.inb = e->rcur[g];
-          it.c0 = n * ch / C;
-          it.c1 = n * (ch + 1) / C;
-          e->ritems.push_back(it);
-        }
-      }
-      i0 = i1;
-    }
-    const int n_items = (int)e->ritems.size();
-    e->d_ritems.ensure(n_items);
-    HIPCHK(hipMemcpyAsync(e->d_ritems.p, e->ritems.data(), n_items * sizeof(RatchetItem),
-                          hipMemcpyHostToDevice, e->stream));
-    // 8-B records address e2 by a 26-bit batch offset; larger batches use 16-B records. A placing
-    // launch writes no records: COUNT, scan, WRITE (compact rows)
-    const bool placing = !no_place && ratchet_placeable(e, stream, B.seq_base, n, full);
-    const int wide = n > ((int64_t)1 << 26) ? 1 : 0;
-    if (n > ((int64_t)1 << 32)) throw Error(SDH_E_INVALID, "batch larger than 2^32 events");
-    e->d_rmatch.ensure((size_t)(e->r_blocks + 1) * e->r_blk_recs * (wide ? 2 : 1));  // (+ the spare block)
-    e->d_rspillA.ensure((size_t)n_items * e->rSC * WAVE);
-    e->d_rlts.ensure((size_t)n_items * e->rML * WAVE);
-    bool any64 = false;
-    for (int g : gs) any64 |= e->rg[g].key_kind == KK_F64 || e->rg[g].key_kind == KK_I64;
-    if (any64) e->d_rspillB.ensure((size_t)n_items * e->rSC * WAVE);
-    e->d_blk_count.ensure((size_t)e->r_blocks);
-    e->d_blk_group.ensure((size_t)e->r_blocks);
-    e->d_blk_side.ensure((size_t)e->r_blocks);
-    e->d_err.ensure(5);
-    HIPCHK(hipMemsetAsync(e->d_err.p, 0, 20, e->stream));
-    HIPCHK(hipMemsetAsync(e->d_blk_next.p, 0, 4, e->stream));
-    HIPCHK(hipMemsetAsync(e->d_rtotal.p, 0, 24, e->stream));
-    // per-tile x summaries for the warm-up scans (rows of this stream's key specs)
-    const int64_t n_tiles = (n + 63) / 64;
-    const size_t n_rows = e->r_sum_specs.size();
-    e->d_tsmax.ensure(n_rows * n_tiles);
-    e->d_tsmin.ensure(n_rows * n_tiles);
-    e->d_tshas.ensure(n_rows * n_tiles);
-    if (!full)
-      for (size_t r = 0; r < n_rows; ++r) {
-        const auto& sp = e->r_sum_specs[r];
-        if (sp[0] != stream) continue;
-        // (the shared-pops form has its own tree: a row only its groups read is not built)
-        bool read = false;
-        for (int g : gs) read = read || (e->rg[g].sum_slot == (int)r && !lshared(g));
-        if (!read) continue;
-        HIPCHK(sdh_launch_ratchet_summary(sp[3], &B, sp[1], sp[2], n_tiles, e->d_tsmax.p + r * n_tiles,
-                                          e->d_tsmin.p + r * n_tiles, e->d_tshas.p + r * n_tiles, e->stream));
-      }
-    RatchetLaunch L{};
-    L.groups = e->d_rg.p;
-    L.full_expiry = full;
-    L.tsum_max = e->d_tsmax.p;
-    L.tsum_min = e->d_tsmin.p;
-    L.tsum_has = e->d_tshas.p;
-    L.n_tiles = n_tiles;
-    L.b = B;
-    L.rsmax = e->rsmax;
-    for (int b = 0; b < 2; ++b) {
-      L.st[b] = e->d_rst[b].p;
-      L.ent_ts[b] = e->d_rts[b].p;
-      L.ent_seq[b] = e->d_rsq[b].p;
-      L.ent_key[b] = e->d_rky[b].p;
-    }
-    L.spillA = e->d_rspillA.p;
-    L.spillB = e->d_rspillB.p;
-    L.match = e->d_rmatch.p;
-    L.blk_count = e->d_blk_count.p;
-    L.blk_side = e->d_blk_side.p;
-    // device records take the 4-B rec4 entries where they can
-    L.rec4 = (devrec && !wide && !full && !no_rec4) ? 1 : 0;
-    L.blk_group = e->d_blk_group.p;
-    L.wide = wide;
-    L.blk_next = e->d_blk_next.p;
-    L.n_blocks = (int32_t)std::min<int64_t>(e->r_blocks, INT32_MAX);
-    L.blk_recs = e->r_blk_recs;
-    L.dev_records = devrec ? 1 : 0;
-    L.rec_total = e->d_rtotal.p;
-    L.err = e->d_err.p;
-    const int nc = e->place_cells[(size_t)stream];
-    const int64_t cells = n * nc + 1;  // (+1: the scan's total)
-    if (placing) {
-      e->p_cnt.ensure((size_t)cells);
-      HIPCHK(hipMemsetAsync(e->p_cnt.p + cells - 1, 0, 4, e->stream));
-      L.pcnt = e->p_cnt.p;
-      L.n_cells = nc;
-    }
-    e->r_placing = false;
-    int any_rec4 = 0, any_shared = 0;
-    // the shared-pops form's buffers for the launch of group g0
-    auto shared_setup = [&](int g0) {
-      SharedLaunch S{};
-      const RatchetGroup& G = e->rg[g0];
-      S.x = (const float*)B.col[G.key_attr];
-      S.n = n;
-      S.xm = G.xmask == sdh::CM_GT ? 0 : G.xmask == (sdh::CM_GT | sdh::CM_EQ) ? 1 : G.xmask == sdh::CM_LT ? 2 : 3;
-      int64_t tot = 0;
-      for (int64_t cur = n; cur > 64 && S.n_lvl < sdh::SH_LEVELS;) {
-        cur = (cur + 63) / 64;
-        S.lvl_n[S.n_lvl++] = cur;
-        tot += cur;
-      }
-      e->d_shtree.ensure((size_t)tot + 1);
-      tot = 0;
-      for (int k = 0; k < S.n_lvl; ++k) {
-        S.lvl[k] = e->d_shtree.p + tot;
-        tot += S.lvl_n[k];
-      }
-      e->d_shkv.ensure((size_t)n * 4);
-      S.nkey = e->d_shkv.p;
-      S.nval = e->d_shkv.p + n;
-      S.skey = e->d_shkv.p + 2 * n;
-      S.sval = e->d_shkv.p + 3 * n;
-      e->d_shpairs.ensure((size_t)n);
-      S.pairs = e->d_shpairs.p;
-      e->d_shcnt.ensure(2);
-      S.cnt = e->d_shcnt.p;
-      const size_t ng = e->rg.size();
-      e->d_shcm.ensure(ng * (size_t)e->rsmax * WAVE);
-      e->d_shcmn.ensure(2 * ng * WAVE);
-      S.cm = e->d_shcm.p;
-      S.cm_n = e->d_shcmn.p;
-      S.cs_n = e->d_shcmn.p + ng * WAVE;
-      e->d_shtemp.ensure(sdh_ratchet_shared_temp(n) + 16);
-      return S;
-    };
-    // one launch per (key kind, orientation, SIM form)
-    auto run = [&](const RatchetLaunch& L0) {
-      for (int i0 = 0; i0 < n_items;) {
-        const int g0 = e->ritems[i0].g;
-        const int kk = e->rg[g0].key_kind, xm = e->rg[g0].xmask, sim = lsim(g0), gate = lgate(g0);
-        int i1 = i0;
-        while (i1 < n_items && lkey(e->ritems[i1].g) == lkey(g0)) ++i1;
-        RatchetLaunch Ls = L0;
-        Ls.items = e->d_ritems.p + i0;
-        Ls.n_items = i1 - i0;
-        int nf = 0;
-        for (int i = i0; i < i1; ++i) nf = std::max(nf, ratchet_nf(e->rg[e->ritems[i].g]));
-        // spill regions are indexed by the item's position in its launch
-        Ls.spillA = e->d_rspillA.p + (size_t)i0 * e->rSC * WAVE;
-        Ls.lds_ts = e->d_rlts.p + (size_t)i0 * e->rML * WAVE;
-        Ls.spillB = any64 ? e->d_rspillB.p + (size_t)i0 * e->rSC * WAVE : nullptr;
-        Ls.rec4 = L0.rec4 && sim && !gate ? 1 : 0;  // (rec4 blocks come from the SIM form only)
-        any_rec4 |= Ls.rec4;
-        if (Ls.rec4 && !Ls.pcnt && !Ls.crow && lshared(g0)) {
-          // one pre-pass per launch = per (stream, key column, OP) of the push
-          const SharedLaunch S = shared_setup(g0);
-          HIPCHK(hipMemsetAsync(S.cnt, 0, 8, e->stream));
-          HIPCHK(sdh_launch_ratchet_shared_pre(&S, &B, e->d_err.p, e->d_shtemp.p, e->d_shtemp.n, e->stream));
-          HIPCHK(sdh_launch_ratchet_shared(&Ls, &S, e->stream));
-          any_shared = 1;
-        } else if (gate) {
-          int ng = 0;
-          for (int i = i0; i < i1; ++i) ng = std::max(ng, e->rg[e->ritems[i].g].n_g);
-          HIPCHK(sdh_launch_gate(kk, xm, full, nf, ng, e->rSC, &Ls, e->stream));
-        } else {
-          HIPCHK(sdh_launch_ratchet(kk, xm, full, nf, full ? 0 : sim, e->rML, e->rSC, &Ls, e->stream));
-        }
-        i0 = i1;
-      }
-    };
-    HIPCHK(hipEventRecord(e->ev0, e->stream));
-    run(L);
-    HIPCHK(hipEventRecord(e->ev1, e->stream));
-    int32_t errs[5], used = 0;
-    HIPCHK(hipMemcpyAsync(errs, e->d_err.p, 20, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&used, e->d_blk_next.p, 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    if (sdh::knob("SDH_TRACE"))
-      fprintf(stderr, "[sdh] ratchet stream %d n %lld attempt %d full %d rec4 %d items %d blocks %d/%lld errs %d %d %d %d %d: %.2f ms\n",
-              stream, (long long)n, attempt, (int)full, L.rec4, n_items, used, (long long)e->r_blocks, errs[0], errs[1],
-              errs[2], errs[3], errs[4], ms);
-    if (errs[3]) throw Error(SDH_E_CAPACITY, "a pending partial is more than 2^31 events old");
-    if (errs[1] && !full) {  // timestamps out of order: exact re-run with the full expiry scan
-      e->r_full_expiry[stream] = 1;
-      continue;
-    }
-    if (errs[0]) {
-      // exact re-run with a larger spill ring (and persisted deques to hold it): the reference's
-      // pending list is unbounded (StreamPreStateProcessor.java:298)
-      if (e->rSC >= (1 << 24))
-        throw Error(SDH_E_CAPACITY, fmt("more than %d pending partials in one pattern", e->rML + e->rSC));
-      e->rSC *= 2;
-      ratchet_grow_rsmax(e, e->rML + e->rSC);
-      continue;
-    }
-    if (errs[2]) {
-      // out of blocks: blk_next ends at the number of blocks the launch's waves asked for (a wave past
-      // the last block writes into the spare one and keeps counting), so one re-run with that many fits
-      const int64_t need = std::max<int64_t>(2 * e->r_blocks, (int64_t)used + used / 64 + 64);
-      const int64_t blk_bytes = (int64_t)e->r_blk_recs * 8 * (wide ? 2 : 1);
-      size_t fr = 0, tot = 0;
-      HIPCHK(hipMemGetInfo(&fr, &tot));
-      const double have = (double)fr + (double)e->d_rmatch.n * 8.0 - (double)(1 << 30);
-      int64_t nb = std::max<int64_t>((int64_t)used + used / 64 + 64, e->r_blocks + 1);
-      if ((double)(need + 1) * blk_bytes <= have) nb = std::max(nb, need);
-      if ((double)(nb + 1) * blk_bytes > have || nb >= INT32_MAX)
-        throw Error(SDH_E_CAPACITY, fmt("the push's match records need %.1f GB of HBM (%.1f GB free): push fewer events "
-                                        "per call", (double)(nb + 1) * blk_bytes / 1e9, have / 1e9));
-      e->r_blocks = nb;
-      continue;
-    }
-    if (errs[4] && L.rec4) {  // a rec4 entry's e1 distance reached 2^26: exact re-run with 8-B records
-      no_rec4 = true;  // (this push only: the next one tries rec4 again)
-      ++e->r_rec4_reruns;
-      continue;
-    }
-    int64_t placed_rows = 0;
-    if (placing) {
-      // the (event, cell) counts -> each cell's first row; then the same items again, writing
-      e->p_ptemp.ensure(sdh_place_temp_bytes(cells));
-      HIPCHK(sdh_place_total(e->p_cnt.p, cells, e->d_rtotal.p + 1, e->stream));
-      HIPCHK(sdh_place_scan(e->p_cnt.p, cells, e->p_ptemp.p, e->p_ptemp.n, e->stream));
-      unsigned long long tot = 0;
-      HIPCHK(hipMemcpyAsync(&tot, e->d_rtotal.p + 1, 8, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      placed_rows = (int64_t)tot;
-      const int64_t n0 = e->mt.n;
-      if (tot >= (unsigned long long)INT32_MAX || n0 + placed_rows >= INT32_MAX) {  // (2^31 rows: table records)
-        no_place = true;
-        continue;
-      }
-      e->pc_rows.grow_keep((size_t)((n0 + placed_rows) * e->cw), (size_t)(n0 * e->cw), e->stream);
-      RatchetLaunch W = L;
-      W.pcnt = nullptr;
-      W.pbase = e->p_cnt.p;
-      W.crow = e->pc_rows.p;
-      W.cw = e->cw;
-      W.row0 = n0;
-      e->r_place_row0 = n0;
-      W.seq_ref = e->seq_ref;
-      float ms2 = 0;
-      HIPCHK(hipEventRecord(e->ev0, e->stream));
-      run(W);
-      HIPCHK(hipEventRecord(e->ev1, e->stream));
-      HIPCHK(hipEventSynchronize(e->ev1));
-      HIPCHK(hipEventElapsedTime(&ms2, e->ev0, e->ev1));
-      ms += ms2;
-    }
-    for (int g : gs) e->rcur[g] ^= 1;
-    e->r_shared_pushes += any_shared;
-    e->r_placing = placing;
-    e->r_blk_taken = used;
-    e->r_seq_base = B.seq_base;
-    if (placing) {
-      e->r_blocks_used = 0;
-      e->r_matches = placed_rows;
-    } else if (devrec) {  // left on the device for sdh_engine_poll_records: the blocks 0 .. used-1
-      unsigned long long tot[3] = {0, 0, 0};
-      HIPCHK(hipMemcpy(tot, e->d_rtotal.p, 24, hipMemcpyDeviceToHost));
-      e->r_blocks_used = used;
-      e->r_matches = (int64_t)tot[0];
-      e->r_rec_bytes = (double)tot[2];
-      e->r_rec4 = any_rec4;
-    } else {
-      e->r_blocks_used = std::min<int>(used, (int)e->r_blocks);
-      e->r_blk_count.resize(e->r_blocks_used);
-      if (e->r_blocks_used)
-        HIPCHK(hipMemcpy(e->r_blk_count.data(), e->d_blk_count.p, e->r_blocks_used * 4, hipMemcpyDeviceToHost));
-      e->r_matches = ratchet_count_matches(e);
-    }
-    e->r_kernel_ms = ms;
-    e->r_wide = wide;
-    // algorithmic bytes: every group streams the batch's operand columns once
-    // (ts + x-atom column + f0 columns; the warm-up re-reads are overhead, not counted), writes
-    // 32 B per match (SURVEY §8(d)'s unit; the device record is 8 B, expanded at poll) and reads +
-    // writes its persisted deques (24 B per pending partial)
-    double bytes = 0;
-    for (int g : gs) {
-      const RatchetGroup& G = e->rg[g];
-      int64_t ev_bytes = 8 + B.width[G.key_attr];
-      for (int a = 0; a < G.n_f0; ++a) {
-        if (G.f0[a].attr != G.key_attr) ev_bytes += B.width[G.f0[a].attr];
-        if (G.f0[a].cur2 && G.f0[a].attr2 != G.key_attr) ev_bytes += B.width[G.f0[a].attr2];
-      }
-      for (int a = 0; a < G.n_g; ++a)  // (K_gate's gate columns)
-        if (G.g[a].attr != G.key_attr) ev_bytes += B.width[G.g[a].attr];
-      bytes += (double)n * ev_bytes;
-    }
-    bytes += (double)e->r_matches * 32.0;
-    e->r_kernel_bytes = bytes;
-    return;
-  }
-  throw Error(SDH_E_CAPACITY, "ratchet launch did not converge");
-}
-
 // ------------------------------------------------------------------------------------------
 // K_gen host side: lowering, instance arenas, partition routing, launch, match collection
 // ------------------------------------------------------------------------------------------
@@ -2063,9 +353,6 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
 // `every e1 -> e2<min:max> -> e3` patterns whose structure the compact partial tables reproduce
 // exactly (the argument is in nfa_part.hip's header)
 // ------------------------------------------------------------------------------------------
-struct KPart {
-  int kind = -1, sA = 1, sB = 2, cmax = 0, n_e1 = 0, n_first = 0, n_last = 0;
-};
 
 // every slot reference of state i's filters: (slot, chain index) pairs; false if an instruction
 // names a slot in another way than OP_ATTR / OP_STREAM_IS_NULL
@@ -2189,285 +476,6 @@ void spec_build(sdh_engine* e) {
     }
   }
   e->stats.spec_kernels = n;
-}
-
-// ------------------------------------------------------------------------------------------
-// K_slab host side (nfa_slab.hip): directory growth with the key table, slab space (reclaiming a
-// sub-ring's oldest half, growing), rollback of a failed push
-// ------------------------------------------------------------------------------------------
-void slab_heads(sdh_engine* e, sdh_engine::SlabSet& ss) {
-  ss.h_head.resize(ss.nsub);
-  HIPCHK(hipMemcpyAsync(ss.h_head.data(), ss.head.p, ss.nsub * 8, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-}
-
-void slab_upload_rings(sdh_engine::SlabSet& ss) {
-  HIPCHK(hipMemcpy(ss.d_ring.p, ss.ring.data(), ss.nsub * sizeof(uint32_t*), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ss.d_cap.p, ss.cap.data(), ss.nsub * 8, hipMemcpyHostToDevice));
-}
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-uint32_t* ring_malloc(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t words) {
-  (void)e;
-  uint32_t* p = ss.alloc_ring(words);
-  if (!p) throw Error(SDH_E_CAPACITY, fmt("device memory exhausted allocating a %.2f GB K_slab ring", words * 4.0 / 1e9));
-  return p;
-}
-
-// fresh, empty sub-rings of `cap` words each
-void slab_init(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t cap) {
-  for (size_t r = 0; r < ss.ring.size(); ++r) ss.free_ring(ss.ring[r], r < ss.cap.size() ? ss.cap[r] : 0);
-  cap = (cap + 3) & ~3ll;
-  ss.ring.assign(ss.nsub, nullptr);
-  ss.cap.assign(ss.nsub, cap);
-  for (auto& p : ss.ring) p = ring_malloc(e, ss, cap);
-  ss.d_ring.ensure(ss.nsub);
-  ss.d_cap.ensure(ss.nsub);
-  slab_upload_rings(ss);
-  ss.head.ensure(ss.nsub);
-  ss.tail.ensure(ss.nsub);
-  ss.head_bak.ensure(ss.nsub);
-  HIPCHK(hipMemset(ss.head.p, 0, ss.nsub * 8));
-  HIPCHK(hipMemset(ss.tail.p, 0, ss.nsub * 8));
-  ss.h_head.assign(ss.nsub, 0);
-  ss.h_tail.assign(ss.nsub, 0);
-  ss.h_push0.assign(ss.nsub, 0);
-  ss.live.ensure(256);
-  ss.live_bak.ensure(256);
-  ss.traffic.ensure(256);
-  HIPCHK(hipMemset(ss.live.p, 0, 256 * 8));
-}
-
-// directory room for `keys` keys (key-major: the old entries are a prefix; new keys' blocks empty)
-void slab_grow_keys(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t keys) {
-  if (keys <= ss.key_cap) return;
-  int64_t cap = std::max<int64_t>(64, ss.key_cap);
-  while (cap < keys) cap *= 2;
-  const size_t old_n = (size_t)ss.key_cap * ss.n_groups, new_n = (size_t)cap * ss.n_groups;
-  DevBuf<uint64_t> nd;
-  if (hipMalloc(&nd.p, new_n * 8) != hipSuccess)
-    throw Error(SDH_E_CAPACITY, fmt("device memory exhausted growing the K_slab directory to %lld keys", (long long)cap));
-  nd.n = new_n;
-  HIPCHK(hipMemsetAsync(nd.p + old_n, 0, (new_n - old_n) * 8, e->stream));
-  if (old_n) HIPCHK(hipMemcpyAsync(nd.p, ss.dir.p, old_n * 8, hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  std::swap(ss.dir.p, nd.p);
-  std::swap(ss.dir.n, nd.n);
-  ss.key_cap = cap;
-}
-
-// One directory pass moving blocks (nfa_slab.hip slab_move_kernel); false if a destination ring
-// ran out of room (nothing is lost: a block keeps its old place until its directory word moves)
-bool slab_move_raw(sdh_engine* e, sdh_engine::SlabSet& ss, uint64_t* dir, uint32_t* const* src_ring,
-                   const int64_t* src_cap, const unsigned long long* src_tail, int src_nsub,
-                   const std::vector<unsigned long long>& limit, const std::vector<uint8_t>& active,
-                   uint32_t* const* dst_ring, const int64_t* dst_cap, unsigned long long* dst_head,
-                   const unsigned long long* dst_tail, int dst_nsub, std::vector<uint8_t>* ring_fail = nullptr) {
-  DevBuf<unsigned long long> d_lim;
-  DevBuf<uint8_t> d_act;
-  d_lim.ensure(limit.size());
-  HIPCHK(hipMemcpyAsync(d_lim.p, limit.data(), limit.size() * 8, hipMemcpyHostToDevice, e->stream));
-  if (!active.empty()) {
-    d_act.ensure(active.size());
-    HIPCHK(hipMemcpyAsync(d_act.p, active.data(), active.size(), hipMemcpyHostToDevice, e->stream));
-  }
-  e->d_err.ensure(4);
-  HIPCHK(hipMemsetAsync(e->d_err.p, 0, 16, e->stream));
-  DevBuf<uint8_t> d_rf;
-  if (ring_fail) {
-    d_rf.ensure(dst_nsub);
-    HIPCHK(hipMemsetAsync(d_rf.p, 0, dst_nsub, e->stream));
-  }
-  HIPCHK(sdh_slab_move(dir, ss.key_cap * ss.n_groups, ss.n_groups, ss.d_group_ew.p, src_ring, src_cap, src_tail,
-                       src_nsub, d_lim.p, active.empty() ? nullptr : d_act.p, dst_ring, dst_cap, dst_head, dst_tail,
-                       dst_nsub, e->d_err.p, ring_fail ? d_rf.p : nullptr, e->stream));
-  int32_t err = 0;
-  HIPCHK(hipMemcpyAsync(&err, e->d_err.p, 4, hipMemcpyDeviceToHost, e->stream));
-  if (ring_fail) {
-    ring_fail->assign(dst_nsub, 0);
-    HIPCHK(hipMemcpyAsync(ring_fail->data(), d_rf.p, dst_nsub, hipMemcpyDeviceToHost, e->stream));
-  }
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return err == 0;
-}
-
-// rings `which` into new buffers of new_cap[r] words holding their live blocks (a batch at a time,
-// so the extra memory is a batch's worth)
-void slab_grow(sdh_engine* e, sdh_engine::SlabSet& ss, const std::vector<int>& which,
-               const std::vector<int64_t>& new_cap) {
-  // (up to 32 rings and 8 GB of new buffers at a time: old and new buffers coexist while a batch
-  // moves, and C5's rings reach GBs each -- 32 at a time took tens of GB on top of the state)
-  const int BATCH = 32;
-  const int64_t BATCH_WORDS = (int64_t)2 << 30;
-  for (size_t b0 = 0, b1 = 0; b0 < which.size(); b0 = b1) {
-    const double t_start = now_ms();
-    std::vector<uint32_t*> nring(ss.ring);
-    std::vector<int64_t> ncap(ss.cap);
-    std::vector<uint8_t> active(ss.nsub, 0);
-    int64_t words = 0;
-    for (b1 = b0; b1 < which.size() && b1 < b0 + BATCH && (b1 == b0 || words + new_cap[b1] <= BATCH_WORDS); ++b1) {
-      const int r = which[b1];
-      ncap[r] = (new_cap[b1] + 3) & ~3ll;
-      nring[r] = ring_malloc(e, ss, ncap[r]);
-      active[r] = 1;
-      words += ncap[r];
-    }
-    DevBuf<uint32_t*> d_nr;
-    DevBuf<int64_t> d_nc;
-    DevBuf<unsigned long long> nh, nt;
-    d_nr.ensure(ss.nsub);
-    d_nc.ensure(ss.nsub);
-    nh.ensure(ss.nsub);
-    nt.ensure(ss.nsub);
-    const double t_alloc = now_ms();
-    HIPCHK(hipMemcpy(d_nr.p, nring.data(), ss.nsub * sizeof(uint32_t*), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_nc.p, ncap.data(), ss.nsub * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(nh.p, 0, ss.nsub * 8));
-    HIPCHK(hipMemset(nt.p, 0, ss.nsub * 8));
-    if (!slab_move_raw(e, ss, ss.dir.p, ss.d_ring.p, ss.d_cap.p, ss.tail.p, ss.nsub,
-                       std::vector<unsigned long long>(ss.nsub, ~0ull), active, d_nr.p, d_nc.p, nh.p, nt.p, ss.nsub))
-      throw Error(SDH_E_CAPACITY, "K_slab: a ring overflowed while growing");
-    std::vector<unsigned long long> moved(ss.nsub);
-    HIPCHK(hipMemcpy(moved.data(), nh.p, ss.nsub * 8, hipMemcpyDeviceToHost));
-    const double t_move = now_ms();
-    for (int r = 0; r < ss.nsub; ++r) {
-      if (!active[r]) continue;
-      ss.free_ring(ss.ring[r], ss.cap[r]);
-      ss.ring[r] = nring[r];
-      ss.cap[r] = ncap[r];
-      ss.h_head[r] = moved[r];
-      ss.h_tail[r] = 0;
-      ss.h_push0[r] = 0;
-    }
-    slab_upload_rings(ss);
-    HIPCHK(hipMemcpy(ss.head.p, ss.h_head.data(), ss.nsub * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ss.tail.p, ss.h_tail.data(), ss.nsub * 8, hipMemcpyHostToDevice));
-    ss.growths += (int64_t)(b1 - b0);
-    if (sdh::knob("SDH_SLAB_TRACE"))
-      fprintf(stderr, "[sdh] slab grow: %zu rings, %.2f GB: alloc %.1f ms, move %.1f ms, free %.1f ms\n", b1 - b0,
-              words * 4e-9, t_alloc - t_start, t_move - t_alloc, now_ms() - t_move);
-  }
-}
-
-// Room for the next push in every ring. The rings are log-structured: a push appends the entries it
-// changes, the old copies die in place. A ring whose free room falls below its live words plus 1.25x
-// what it took in the last push is cleaned in place: every block written before that push moves to
-// its head (the blocks of the last push are current) -- the oldest 4x the room the next push needs
-// (SDH_SLAB_SPAN), mostly dead copies -- once its free room falls below 5x that need (SDH_SLAB_CLEAN_AT):
-// a few pushes per cleaning, each a directory pass. A ring below 1.4x (live + headroom) words (SDH_SLAB_GROW_AT) moves
-// its live blocks into a fresh buffer of 1.6x that (SDH_SLAB_GROW_TO): the reservation stays
-// under 2x the live words, and the cleaning moves (wave-cooperative, nfa_slab.hip) are cheap enough
-// to run at most pushes. A push that still overflows is undone and re-run with room for 1.25x its
-// demand (re-runs cost time, never matches).
-// (C5: cleaning only when a push lacked room never fit in place -- the ring was full by then -- so
-// every cleaning reallocated; growing by the ring's span instead of its live words doubled the
-// reservation every other step and ran out of HBM.)
-// demand: words a failed push tried to take per ring (room for 1.25x that is made instead)
-void slab_prepare(sdh_engine* e, sdh_engine::SlabSet& ss, const std::vector<int64_t>* demand = nullptr) {
-  const double t_prep = now_ms();
-  std::vector<int64_t> need(ss.nsub);
-  std::vector<unsigned long long> limit(ss.nsub);
-  std::vector<uint8_t> clean(ss.nsub, 0);
-  // live words per ring (one pass over the directory)
-  std::vector<unsigned long long> live(ss.nsub, 0);
-  {
-    DevBuf<unsigned long long> acc;
-    acc.ensure(ss.nsub);
-    HIPCHK(hipMemsetAsync(acc.p, 0, ss.nsub * 8, e->stream));
-    HIPCHK(sdh_slab_live_words_ring(ss.dir.p, ss.key_cap * ss.n_groups, ss.n_groups, ss.d_group_ew.p, ss.nsub, acc.p,
-                                    e->stream));
-    HIPCHK(hipMemcpyAsync(live.data(), acc.p, ss.nsub * 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-  }
-  bool any = false;
-  for (int r = 0; r < ss.nsub; ++r) {
-    const int64_t alloc = (int64_t)(ss.h_head[r] - ss.h_push0[r]);
-    need[r] = std::max<int64_t>(alloc + alloc / 4, 4096);
-    if (demand) need[r] = std::max<int64_t>(need[r], (*demand)[r] + (*demand)[r] / 4);
-    const int64_t used = (int64_t)(ss.h_head[r] - ss.h_tail[r]);
-    // clean once the room falls below SDH_SLAB_CLEAN_AT x the push's need (then the live blocks of
-    // the span still fit at the head: the in-place move needs room for them, and a span holds at most
-    // SDH_SLAB_SPAN x need live words)
-    const double clean_at = sdh::knob("SDH_SLAB_CLEAN_AT") ? atof(sdh::knob("SDH_SLAB_CLEAN_AT")) : 3.0;
-    if ((double)(ss.cap[r] - used) >= clean_at * (double)need[r]) continue;
-    // the oldest quarter of the ring (at least twice the headroom): mostly dead copies, so the move
-    // is small (SDH_SLAB_CLEAN=all: everything before the last push)
-    const unsigned long long cur = ss.h_push0[r] > ss.h_tail[r] ? ss.h_push0[r] : ss.h_head[r];
-    const bool all = sdh::knob("SDH_SLAB_CLEAN") && !strcmp(sdh::knob("SDH_SLAB_CLEAN"), "all");
-    // (the span a push needs, not a fixed share of the ring: every live block in it moves, and the
-    // oldest blocks of a ring are not all dead -- a quarter of the ring per push moved 15 % of C5's
-    // device time. C5 sweep, CLEAN_AT:SPAN:GROW_TO -> slab_move share of the 24-step run, ms/step,
-    // reserved/live: 5:4:1.6 10.0 %, 457, 1.80; 3:2:1.6 7.8 %, 458, 1.95; 3:2:1.5 8.8 %, 447, 1.75;
-    // 4:3:1.6 9.0 %, 469, 1.96; 5:8:1.6 30 %, 632; 9:8:1.6 42 %, 822; GROW_TO 2.0 at 5:4 5.9 %, 2.13)
-    const double span_x = sdh::knob("SDH_SLAB_SPAN") ? atof(sdh::knob("SDH_SLAB_SPAN")) : 2.0;
-    const unsigned long long span = (unsigned long long)std::max<int64_t>((int64_t)(span_x * need[r]), 4096);
-    limit[r] = all ? cur : std::min<unsigned long long>(cur, ss.h_tail[r] + span);
-    clean[r] = 1;
-    any = true;
-  }
-  std::vector<int> grow;
-  std::vector<int64_t> gcap;
-  if (any) {
-    // (a ring's blocks move within that ring, so rings succeed or fail on their own)
-    std::vector<uint8_t> fail;
-    (void)slab_move_raw(e, ss, ss.dir.p, ss.d_ring.p, ss.d_cap.p, ss.tail.p, ss.nsub, limit, clean, ss.d_ring.p,
-                        ss.d_cap.p, ss.head.p, ss.tail.p, ss.nsub, &fail);
-    slab_heads(e, ss);
-    for (int r = 0; r < ss.nsub; ++r)
-      if (clean[r] && !fail[r]) ss.h_tail[r] = limit[r];
-    HIPCHK(hipMemcpy(ss.tail.p, ss.h_tail.data(), ss.nsub * 8, hipMemcpyHostToDevice));
-    ++ss.cleanings;
-    // a ring below 2x (live + headroom) cannot clean in place for long: a fresh buffer of 2.5x that
-    // takes its live blocks (slab_grow compacts as it moves; sized from the live words, not the
-    // ring's span, which counts dead blocks: sizing from the span doubled the reservation every
-    // other C5 step and ran out of HBM)
-    const double grow_at = sdh::knob("SDH_SLAB_GROW_AT") ? atof(sdh::knob("SDH_SLAB_GROW_AT")) : 1.4;
-    const double grow_to = sdh::knob("SDH_SLAB_GROW_TO") ? atof(sdh::knob("SDH_SLAB_GROW_TO")) : 1.5;
-    for (int r = 0; r < ss.nsub; ++r) {
-      if (!clean[r]) continue;
-      const int64_t used = (int64_t)(ss.h_head[r] - ss.h_tail[r]);
-      const double base = (double)((int64_t)live[r] + need[r]);
-      if (!fail[r] && ss.cap[r] - used >= need[r] && (double)ss.cap[r] >= grow_at * base) continue;
-      grow.push_back(r);
-      gcap.push_back(std::max<int64_t>(ss.cap[r], (int64_t)(grow_to * base)));
-    }
-  }
-  if (sdh::knob("SDH_SLAB_TRACE")) {
-    fprintf(stderr, "[sdh] slab prepare: live pass + cleaning %.1f ms\n", now_ms() - t_prep);
-    int64_t c = 0, u = 0, nd = 0, g = 0;
-    for (int r = 0; r < ss.nsub; ++r) {
-      c += ss.cap[r];
-      u += (int64_t)(ss.h_head[r] - ss.h_tail[r]);
-      nd += need[r];
-    }
-    for (int64_t x : gcap) g += x;
-    fprintf(stderr, "[sdh] slab prepare: %d rings, cap %.2f GB, used %.2f GB, need %.2f GB, demand %d, grow %zu rings to %.2f GB\n",
-            ss.nsub, c * 4e-9, u * 4e-9, nd * 4e-9, demand ? 1 : 0, grow.size(), g * 4e-9);
-  }
-  if (!grow.empty()) slab_grow(e, ss, grow, gcap);
-  ss.h_push0 = ss.h_head;
-}
-
-// undo this pass's launch of the set (its directory changes; its allocations are dropped)
-void slab_rollback(sdh_engine* e, sdh_engine::SlabSet& ss) {
-  if (ss.items <= 0) return;
-  HIPCHK(sdh_slab_rollback(ss.dir.p, ss.journal.p, ss.journal_idx.p, ss.items, ss.live_bak.p, ss.live.p, e->stream));
-  HIPCHK(hipMemcpyAsync(ss.head.p, ss.head_bak.p, ss.nsub * 8, hipMemcpyDeviceToDevice, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  ss.items = 0;
-  slab_heads(e, ss);
-}
-
-int64_t slab_live_partials(sdh_engine* e, const sdh_engine::SlabSet& ss) {
-  long long v[256];
-  HIPCHK(hipMemcpyAsync(v, ss.live.p, sizeof v, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  int64_t n = 0;
-  for (long long x : v) n += x;
-  return n;
 }
 
 void gen_build(sdh_engine* e, const std::vector<int>& qis) {

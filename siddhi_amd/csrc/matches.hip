@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include "launchers.h"
 #include "nfa_types.h"
 
 namespace sdh {
@@ -634,7 +635,7 @@ extern "C" hipError_t sdh_place_scan(int32_t* cnt, int64_t cells, void* temp, si
 }
 
 // the exact int64 total of the (event, cell) counts before the int32 scan: a push with 2^31 matches
-// or more would wrap the scan's offsets (engine.hip then takes the table path)
+// or more would wrap the scan's offsets (engine_ratchet.hip then takes the table path)
 __global__ __launch_bounds__(256) void place_total_kernel(const int32_t* __restrict__ cnt, int64_t cells,
                                                           unsigned long long* __restrict__ tot) {
   unsigned long long a = 0;

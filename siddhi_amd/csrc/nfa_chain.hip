@@ -31,6 +31,7 @@
 // the range it reads (err[1]); the host re-runs the batch unchunked otherwise.
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
 #include "nfa_types.h"
 
 namespace sdh {

@@ -36,6 +36,7 @@
 // g-passing events cannot move the reductions either), as in K_ratchet's warm-up.
 // Output: K_ratchet's per-wave blocks of 8-B records {e2 offset | lane << 26, e1 seq low 32} (16-B
 // past 2^26-event batches), decoded by the same readers (matches.hip; sdh_records part 1).
+#include "launchers.h"
 #include "ratchet_common.h"
 
 namespace sdh {

@@ -17,6 +17,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "dev_common.h"
+#include "launchers.h"
 #include "seq_body.h"
 
 namespace sdh {

@@ -3,6 +3,7 @@
 // code for shapes that fill at least two waves.
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
 #include "part_body.h"
 
 namespace sdh {

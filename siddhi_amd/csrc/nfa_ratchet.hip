@@ -29,6 +29,7 @@
 // conflict-free ds_read/write_b128); the top key, bottom ts and bottom seq are cached in VGPRs so an
 // event that pops nothing touches no LDS. Matches are compacted with ballot + mbcnt into
 // per-wave output blocks (one atomic per 8K records). No MFMA: compare/branch work.
+#include "launchers.h"
 #include "ratchet_common.h"
 
 #ifndef SDH_RATCHET_UNROLL

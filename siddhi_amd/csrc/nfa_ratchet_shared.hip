@@ -2,6 +2,7 @@
 // (nfa_ratchet.hip) computed once per push instead of once per 64-pattern group.
 #include <hipcub/hipcub.hpp>
 
+#include "launchers.h"
 #include "ratchet_common.h"
 
 #ifndef SDH_RATCHET_NOSTORE

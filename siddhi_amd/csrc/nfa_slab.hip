@@ -26,6 +26,7 @@
 
 #include "knobs.h"
 #include "dev_common.h"
+#include "launchers.h"
 #include "slab.h"
 
 namespace sdh {

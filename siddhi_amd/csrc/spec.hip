@@ -39,7 +39,7 @@ std::string tuning_defines() {
   return d;
 }
 
-// an integer knob from the environment, clamped (tuning A/Bs of the generated kernels)
+// an integer knob (sdh::knob: the engine's sdh_config.debug), clamped (tuning A/Bs of the generated kernels)
 int env_int(const char* env, int dflt, int lo, int hi) {
   const char* v = sdh::knob(env);
   const int n = v && *v ? atoi(v) : dflt;

@@ -7,7 +7,7 @@ receivers with their processor registration order, and the inner-state-runtime t
 ``init``/``reset``/``update``.  Filters and selector outputs are typed postfix bytecode.
 
 Binary layout (little-endian int64 words; the C-ABI's specification is ``include/siddhi_hip_ir.h``),
-consumed by the engine (``siddhi_amd/csrc/engine.hip`` ``read_ir`` and ``siddhi_amd/csrc/gen_lower.h``
+consumed by the engine (``siddhi_amd/csrc/engine_lower.hip`` ``read_ir`` and ``siddhi_amd/csrc/gen_lower.h``
 ``kg::read_program``) and by the CPU oracle (``oracle/oracle.cpp``)::
 
     'SDHIR001' version
