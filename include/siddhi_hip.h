@@ -57,7 +57,9 @@ extern "C" {
 #define SDH_E_INVALID (-1)     /* bad argument / malformed IR                               */
 #define SDH_E_UNSUPPORTED (-2) /* query shape not executable on the GPU path                */
 #define SDH_E_DEVICE (-3)      /* HIP runtime error                                          */
-#define SDH_E_CAPACITY (-4)    /* a partial-match table or match buffer overflowed (see below) */
+#define SDH_E_CAPACITY (-4)    /* a capacity the caller fixed was passed (partials_per_inst > 0,   */
+                               /* an output array), or device memory ran out while a buffer grew; */
+                               /* growing buffers (see below) do not fail otherwise                */
 #define SDH_E_REFERENCE (-5)   /* the reference engine would throw here (e.g. CME)           */
 
 typedef struct sdh_engine sdh_engine;
@@ -69,7 +71,16 @@ typedef struct sdh_config {
                              /*   queries run on every rank for the keys this rank owns:       */
                              /*   |String.valueOf(key).hashCode() % shard_world| == shard_rank */
                              /*   (PartitionedDistributionStrategy.java:98-109)                */
-  int32_t partials_per_inst; /* live partial-match capacity per query instance (mult. of 64) */
+  /* K_chain partial-match tables (unpartitioned stream-state chains), per query:
+   *   0      growing (the default): the tables start at 128 partials and a push that overflows them
+   *          is re-run exactly at a larger size (sdh_stats.pool_regrows), 256 and 512 in registers,
+   *          beyond that paged in HBM -- the reference's pending lists are unbounded
+   *          (StreamPreStateProcessor.java:59-60); the only limit is device memory;
+   *   n > 0  a fixed capacity the caller chose: 64, 128, 256 or 512 (n rounded up; larger values
+   *          mean 512). A push that needs more fails with SDH_E_CAPACITY.
+   * sdh_engine_restore: a growing engine adopts the snapshot's capacity; a fixed engine takes
+   * snapshots of its own capacity only (SDH_E_INVALID otherwise).                               */
+  int32_t partials_per_inst;
   int64_t max_batch;         /* max events per push                                          */
   int64_t match_capacity;    /* max matches held between polls (0 = sized automatically)     */
   int32_t chunk_events;      /* target events per parallel chunk (0 = automatic)             */
@@ -177,8 +188,9 @@ typedef struct sdh_stats {
   int64_t ingest_bytes;      /* bytes copied from host batches so far                         */
   int64_t spec_kernels;      /* shape-compiled kernels this engine launches (hiprtc at create; */
                              /* SDH_SPEC=0 off, 1 every shape, default shapes of >= 128 queries) */
-  int64_t pool_regrows;      /* K_gen pool / list growths (each re-lays the arenas and re-runs   */
-                             /* the push that overflowed; the reference's lists are unbounded)   */
+  int64_t pool_regrows;      /* K_gen pool / list and K_chain table growths (each re-lays the     */
+                             /* state and re-runs the push that overflowed; the reference's lists */
+                             /* are unbounded)                                                    */
   int64_t last_slab_items;   /* K_slab work items of the last push: key segments x groups         */
   int64_t placed_pushes;     /* pushes whose matches (all K_ratchet) went straight to their R18   */
                              /* rows (no sort at poll; matches.hip ratchet_place_kernel)          */
@@ -276,7 +288,10 @@ int sdh_engine_pending_matches(sdh_engine* e, int64_t* n);
  *    A K_part record's key id is a dense id: f_query_keys[query][id] is the raw partition key (the
  *    sdh_matches.key value; f_query_keys[query] is NULL for an unpartitioned query).
  * 3. K_chain segments (the general chain plan): c_items segments, segment i = c_count[i] records of
- *    c_words int64 at c_base + c_off[i] * c_words, each {query, ts, seq_0 .. seq_{S-1}}.
+ *    c_words int64 at c_base + c_off[i] * c_words, each {query, ts, seq_0 .. seq_{S-1}}. A segment's
+ *    records are in no particular order either: past 512 partials per query the kernel walks its
+ *    table page by page, not event by event. A push that grew the tables and ran again hands out
+ *    the records of the run that succeeded only.
  */
 #define SDH_REC_NONE 0
 #define SDH_REC_8 1

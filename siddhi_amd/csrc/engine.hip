@@ -2406,9 +2406,14 @@ int sdh_engine_create(const void* ir, size_t len, const sdh_config* cfg, sdh_eng
       if (rp.ok) rplans.push_back({rp, qi});
       else e->lq.push_back(L);
     }
+    // K_chain tables: a capacity the caller chose is fixed (SDH_E_CAPACITY lies past it); 0 starts at
+    // 128 partials per query and grows on overflow (chain_grow), past 512 in the paged form
     int want = e->cfg.partials_per_inst > 0 ? e->cfg.partials_per_inst : 128;
     e->K = want <= 64 ? 1 : want <= 128 ? 2 : want <= 256 ? 4 : 8;
     e->pcap = 64 * e->K;
+    e->chain_growing = e->cfg.partials_per_inst <= 0;
+    if (const char* v = sdh::knob("SDH_CHAIN_PAGED")) e->chain_force_paged = atoi(v) != 0;
+    e->chain_paged = e->chain_force_paged;
     int maxS = rplans.empty() ? 1 : 2;
     for (auto& L : e->lq) maxS = std::max(maxS, L.cq.n_states);
     e->rec_words = 2 + maxS;
@@ -2832,7 +2837,7 @@ int sdh_engine_stats(sdh_engine* e, sdh_stats* out) {
     for (auto& ss : e->ssets) live += slab_live_partials(e, *ss);
     live += device_live_partials(e);
     e->stats.live_partials = live;
-    e->stats.pool_regrows = e->gen_regrows;
+    e->stats.pool_regrows = e->gen_regrows + e->chain_regrows;
     e->stats.last_slab_items = e->slab_items;
     // queries per plan: K_ratchet, K_gate, K_chain, K_part, K_slab, K_seq, K_gen
     for (auto& c : e->stats.plan_queries) c = 0;
@@ -3051,7 +3056,12 @@ int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len) {
     if (nx() != SNAP_MAGIC) throw Error(SDH_E_INVALID, "bad snapshot magic");
     if (nx() != SNAP_VERSION) throw Error(SDH_E_INVALID, "snapshot of another format version");
     const size_t nq = (size_t)nx();
-    if (nq != e->lq.size() || nx() != e->pcap) throw Error(SDH_E_INVALID, "snapshot of a different program");
+    const int64_t spcap = nx();  // the snapshot's K_chain table capacity
+    if (nq != e->lq.size() || spcap < 64 || spcap % 64 || spcap > (1 << 24))
+      throw Error(SDH_E_INVALID, "snapshot of a different program");
+    if (spcap != e->pcap && !e->chain_growing)
+      throw Error(SDH_E_INVALID, fmt("snapshot of K_chain tables of %lld partials per query: this engine's are fixed at "
+                                     "%d (partials_per_inst)", (long long)spcap, e->pcap));
     const int64_t b32 = nx(), b64 = nx();
     kg::Sizing sz;
     sz.R = (int)nx();
@@ -3069,13 +3079,21 @@ int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len) {
     const size_t ns = (size_t)nx();
     if (ns != e->prev_ts.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
     for (auto& t : e->prev_ts) t = nx();
-    const size_t tbl = (size_t)NF * e->pcap;
+    // a growing engine adopts the snapshot's larger tables; smaller ones load into the lanes they have
+    if (spcap > e->pcap) chain_grow(e, spcap);
+    const size_t tbl = (size_t)NF * e->pcap, stbl = (size_t)NF * spcap;
+    std::vector<int64_t> rows(tbl);
     for (size_t q = 0; q < nq; ++q) {
       InstHeader h{(int32_t)nx(), (int32_t)nx(), 0, 0};
-      if (i + tbl > nw) throw Error(SDH_E_INVALID, "snapshot truncated");
+      if (i + stbl > nw) throw Error(SDH_E_INVALID, "snapshot truncated");
+      for (int f = 0; f < NF; ++f) {
+        int64_t* row = rows.data() + (size_t)f * e->pcap;
+        std::copy(&w[i + (size_t)f * spcap], &w[i + (size_t)(f + 1) * spcap], row);
+        std::fill(row + spcap, row + e->pcap, f == F_STATE ? -1 : 0);
+      }
       HIPCHK(hipMemcpy(e->d_hdr[e->cur[q]].p + q, &h, sizeof h, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_part[e->cur[q]].p + q * tbl, &w[i], tbl * 8, hipMemcpyHostToDevice));
-      i += tbl;
+      HIPCHK(hipMemcpy(e->d_part[e->cur[q]].p + q * tbl, rows.data(), tbl * 8, hipMemcpyHostToDevice));
+      i += stbl;
     }
     const size_t ng = (size_t)nx();
     if (ng != e->rg.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");

@@ -220,6 +220,11 @@ struct sdh_engine {
   IProgram prog;
   std::vector<Lowered> lq;           // local (this shard's) queries
   int K = 1, pcap = 64, rec_words = 3;
+  // K_chain tables: partials_per_inst == 0 grows them on overflow (chain_grow), past 512 partials or
+  // under SDH_CHAIN_PAGED in the paged form (nfa_chain.hip), whose earlier chunks work in d_pscratch
+  bool chain_growing = false, chain_paged = false, chain_force_paged = false;
+  int64_t chain_regrows = 0;         // table growths so far (sdh_stats.pool_regrows)
+  DevBuf<int64_t> d_pscratch;
   DevBuf<ChainQuery> d_q;
   DevBuf<InstHeader> d_hdr[2];
   DevBuf<int64_t> d_part[2];
@@ -580,6 +585,7 @@ RatchetPlan ratchet_plan(const ChainQuery& c);
 // engine_ratchet.hip
 void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
             const std::vector<int>& qs, bool allow_chunks, bool* unordered);
+void chain_grow(sdh_engine* e, int64_t want);
 void ratchet_build(sdh_engine* e, std::vector<std::pair<RatchetPlan, int>>& plans);
 void ratchet_grow_rsmax(sdh_engine* e, int64_t want);
 void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2]);

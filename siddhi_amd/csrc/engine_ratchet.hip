@@ -5,8 +5,77 @@
 namespace sdh {
 namespace eng {
 
+namespace {
+int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
+                    const std::vector<int>& qs, bool allow_chunks, bool* unordered);
+}
+
+// K_chain tables with room for `want` partials per query: both buffers re-laid on the device
+// ([q][field][pcap]: the field rows move, the new lanes are free). Up to 512 partials the sizes are
+// 64, 128, 256 and 512 (the K register sets of nfa_chain_kernel, which one-state queries keep using
+// beside the paged form, cover exactly 64 * K lanes); beyond that any multiple of 64 (the paged form)
+void chain_grow(sdh_engine* e, int64_t want) {
+  int64_t cap = e->pcap;
+  if (want <= 512) {
+    while (cap < want) cap *= 2;
+  } else {
+    cap = std::max<int64_t>(cap, (want + 63) / 64 * 64);
+  }
+  if (cap <= e->pcap) return;
+  if (cap > (1 << 24)) throw Error(SDH_E_CAPACITY, "more than 2^24 pending partials in one chain pattern");
+  const int64_t rows = (int64_t)std::max<size_t>(e->lq.size(), 1) * NF;
+  DevBuf<int64_t> nw[2];
+  for (int b = 0; b < 2; ++b) {
+    if (hipMalloc(&nw[b].p, (size_t)rows * cap * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      nw[b].p = nullptr;
+      throw Error(SDH_E_CAPACITY, fmt("device memory exhausted growing the K_chain tables to %lld partials per query",
+                                      (long long)cap));
+    }
+    nw[b].n = (size_t)rows * cap;
+    HIPCHK(sdh_chain_relayout(e->d_part[b].p, nw[b].p, rows, e->pcap, (int)cap, e->stream));
+  }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (int b = 0; b < 2; ++b) {
+    std::swap(e->d_part[b].p, nw[b].p);
+    std::swap(e->d_part[b].n, nw[b].n);
+  }
+  e->pcap = (int)cap;
+  e->K = cap <= 64 ? 1 : cap <= 128 ? 2 : cap <= 256 ? 4 : 8;
+  e->chain_paged = e->chain_force_paged || cap > 512;
+  ++e->chain_regrows;
+}
+
+// One K_chain step of the queries `qs` over batch B. A table overflow of a growing engine
+// (partials_per_inst == 0) is re-run here at a larger table: the kernels read part[cur] and write
+// part[1 - cur], and cur flips only after this returns (do_push), so the input tables are intact when
+// err[0] comes back and the re-run is exact by construction. Every attempt plans its items, segments
+// and counts afresh, so a failed one leaves nothing behind.
 void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
             const std::vector<int>& qs, bool allow_chunks, bool* unordered) {
+  double ms_failed = 0;
+  for (;;) {
+    const int32_t need = launch_once(e, stream, B, t01, qs, allow_chunks, unordered);
+    e->stats.last_kernel_ms += ms_failed;
+    if (need < 0) return;
+    ms_failed = e->stats.last_kernel_ms;
+    // the register forms can only double; the paged form counted what it could not store, so one
+    // re-run fits (with an eighth of headroom, and at most 8x: a long push counts partials as lost
+    // that would have expired had they been stored)
+    int64_t want = 2 * (int64_t)e->pcap;
+    if (e->chain_paged)
+      want = std::min<int64_t>(8 * (int64_t)e->pcap, std::max<int64_t>(want, (int64_t)need + need / 8));
+    if (sdh::knob("SDH_TRACE"))
+      fprintf(stderr, "[sdh] chain tables %d -> %lld partials per query (needed %d)\n", e->pcap, (long long)want, need);
+    chain_grow(e, want);
+  }
+}
+
+namespace {
+// one attempt; returns -1, or after a table overflow of a growing engine the partials per query the
+// paged form asked for (the register forms: 0)
+int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
+                    const std::vector<int>& qs, bool allow_chunks, bool* unordered) {
   const int64_t n = B.n;
   // chunk planning: enough waves to fill 256 CUs, chunks >> the warm-up window
   double ev_per_ms = 1.0;
@@ -22,11 +91,19 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
   }
   const double T = std::max({2.0 * max_warm, (double)n * qs.size() / target_waves, 2.0 * min_chunk});
   e->work.clear();
-  int64_t seg = 0;
+  int64_t seg = 0, scr = 0;
   // queries grouped by state count (one kernel instantiation per group)
   std::vector<int> order(qs);
   std::stable_sort(order.begin(), order.end(),
                    [&](int a, int b) { return e->lq[a].cq.n_states < e->lq[b].cq.n_states; });
+  // the paged form runs the queries that hold partials (two states or more). Each chunk but a query's
+  // last works in a scratch table of pcap entries; together they take at most 1 GiB,
+  // which bounds the chunks per paged query
+  auto paged = [&](int li) { return e->chain_paged && e->lq[li].cq.n_states >= 2; };
+  int64_t n_paged = 0;
+  for (int li : order) n_paged += paged(li) ? 1 : 0;
+  const int64_t tbl_bytes = (int64_t)NF * e->pcap * 8;
+  const int64_t paged_chunks = 1 + ((int64_t)1 << 30) / (tbl_bytes * std::max<int64_t>(1, n_paged));
   for (int li : order) {
     const ChainQuery& c = e->lq[li].cq;
     int64_t C = 1;
@@ -34,6 +111,7 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
       const double warm = (double)c.within * ev_per_ms + 64.0;
       const double emit_len = std::max((double)min_chunk, T - warm);
       C = std::max<int64_t>(1, (int64_t)std::ceil((double)n / emit_len));
+      if (paged(li)) C = std::min(C, paged_chunks);
     }
     for (int64_t ch = 0; ch < C; ++ch) {
       WorkItem w{};
@@ -46,10 +124,12 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
       w.seg_off = seg;
       w.seg_cap = (w.c1 - w.c0) + e->pcap + 1;
       seg += w.seg_cap;
+      w.scr = paged(li) && ch + 1 < C ? scr++ : -1;
       e->work.push_back(w);
     }
   }
   const int n_items = (int)e->work.size();
+  if (scr > 0) e->d_pscratch.ensure((size_t)scr * NF * e->pcap);
   e->d_work.ensure(n_items);
   e->d_seg_count.ensure(n_items);
   e->d_match.ensure((size_t)seg * e->rec_words);
@@ -71,6 +151,7 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
   L.rec_words = e->rec_words;
   L.seg_count = e->d_seg_count.p;
   L.err = e->d_err.p;
+  L.scratch = e->d_pscratch.p;
   const size_t lds = 0;
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   for (int i0 = 0; i0 < n_items;) {
@@ -81,7 +162,8 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
     Ls.work = e->d_work.p + i0;
     Ls.seg_count = e->d_seg_count.p + i0;
     Ls.n_work = i1 - i0;
-    HIPCHK(sdh_launch_chain(S, e->K, &Ls, (Ls.n_work + 3) / 4, lds, e->stream));
+    if (paged(e->work[i0].q)) HIPCHK(sdh_launch_chain_paged(S, &Ls, (Ls.n_work + 3) / 4, e->stream));
+    else HIPCHK(sdh_launch_chain(S, e->K, &Ls, (Ls.n_work + 3) / 4, lds, e->stream));
     i0 = i1;
   }
   HIPCHK(hipEventRecord(e->ev1, e->stream));
@@ -94,7 +176,11 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   e->stats.last_kernel_ms = ms;
-  if (errs[0]) throw Error(SDH_E_CAPACITY, "partial-match table overflow: raise partials_per_inst");
+  if (errs[0]) {
+    if (!e->chain_growing)
+      throw Error(SDH_E_CAPACITY, "partial-match table overflow: raise partials_per_inst (0: tables grow)");
+    return std::max(0, errs[3]);
+  }
   if (errs[2]) throw Error(SDH_E_CAPACITY, "match segment overflow");
   *unordered = errs[1] != 0;
   // algorithmic bytes of this launch: every item streams its [w0, c1) events once
@@ -114,7 +200,9 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
   bytes += (double)total_matches * e->rec_words * 8;
   e->stats.last_kernel_bytes = bytes;
   e->device_matches = total_matches;
+  return -1;
 }
+}  // namespace
 
 // ------------------------------------------------------------------------------------------
 // K_ratchet host side

@@ -58,6 +58,9 @@ extern "C" hipError_t sdh_gen_remap(const int32_t* lane_q, int group_base, int n
 
 extern "C" hipError_t sdh_launch_chain(int n_states, int k, const sdh::ChainLaunch* L, int n_blocks,
                                        size_t lds, hipStream_t s);
+extern "C" hipError_t sdh_launch_chain_paged(int n_states, const sdh::ChainLaunch* L, int n_blocks, hipStream_t s);
+extern "C" hipError_t sdh_chain_relayout(const int64_t* src, int64_t* dst, int64_t rows, int old_cap, int new_cap,
+                                         hipStream_t s);
 extern "C" hipError_t sdh_launch_ratchet(int key_kind, int xmask, int full, int nf, int sim, int ML, int SC,
                                          const sdh::RatchetLaunch* L, hipStream_t s);
 extern "C" int sdh_ratchet_occupancy(int key_kind, int full, int nf, int ML, int sim);

@@ -29,6 +29,37 @@
 // events from w0 = lower_bound(ts, ts[c0-1] - T) without emitting; any partial older than w0
 // has expired by event c0-1. Requires non-decreasing timestamps, which every wave verifies on
 // the range it reads (err[1]); the host re-runs the batch unchunked otherwise.
+//
+// Paged form (nfa_chain_paged_kernel; more than 512 partials per query, or SDH_CHAIN_PAGED): the
+// reference's pending lists are unbounded (StreamPreStateProcessor.java:59-60, :203-216, walked in
+// full at :298) and registers end at 64 * 8 partials, so past that the table stays in HBM, same
+// field-major layout, in pages of 64 entries (one coalesced load per field). The walk is entry-major
+// per 64-event tile: the tile is staged as above, then every live page is loaded into one register
+// set, sees the tile's events in order, and is stored back compacted; the partials the seed opens
+// in the tile form one fresh page -- lane k holds the one opened at event k, takes part in the
+// events after k only -- whose survivors are appended at the tail. The register form walks
+// event-major (each event through every partial). Both give the same matches and the same state:
+//   * a chain partial's fate depends on the events and its own words only: no partial reads another,
+//     and the seed is stateless (`every` re-arms it unchanged; without `every` the first passing
+//     event consumes it, which the staged smask[0] alone decides);
+//   * each partial sees the same events in the same order in both walks: a partial opened or
+//     advanced at event j is next examined at j + 1 (states are swept last to first, so the advanced
+//     partial is not seen again at j; the fresh page's lane k joins after event k's sweep), and a page
+//     runs the tile's events k = 0 .. cnt-1 in order, tiles in order; so lazy expiry (checked when an
+//     event of the state's stream arrives, before the filter) fires at the same event as well;
+//   * what differs is the order in which the matches of one push leave the kernel (page by page,
+//     not event by event) and the lanes the survivors end in. Neither is observable: the match table
+//     orders rows by trigger seq, receiver rank and the slot seqs (nfa_types.h, MatchTable), device
+//     records promise no order within a segment (include/siddhi_hip.h), and a table lane's index
+//     is read by nothing.
+// Stores go to a write cursor that never passes the read cursor (a page stores at most the 64 entries
+// it loaded, from registers), so the table is compacted in place: the first tile of an item that
+// continues the persisted state reads part[inb] (holes allowed) and writes the working table, later
+// tiles read and write the working table. The working table of a query's last chunk is part[1 - inb];
+// the earlier chunks' are scratch tables of the same capacity (a chunk's live partials are a subset of
+// the unchunked run's at the same event, so no chunk needs more than the table does). A tail past the
+// capacity sets err[0], and the item goes on counting what it could not store (err[3]), so the host
+// re-runs the push once at a size that fits -- part[inb] is read, never written, until then.
 #include <hip/hip_runtime.h>
 
 #include "launchers.h"
@@ -441,6 +472,328 @@ __global__ __launch_bounds__(256) void nfa_chain_kernel(ChainLaunch L) {
   }
 }
 
+// ---- the paged form (header: "Paged form") ----
+
+// page entry li of a field-major table with `cap` lanes per field; the fields the query does not use
+// (slots past S - 2, captures past n_cap) are neither read nor written
+template <int S>
+__device__ __forceinline__ void page_load(const int64_t* tab, int cap, int li, int n_cap, PSet& P) {
+  P.ts0 = tab[F_TS0 * cap + li];
+#pragma unroll
+  for (int s = 0; s < MAXS - 1; ++s) P.sq[s] = s < S - 1 ? tab[(F_SEQ0 + s) * cap + li] : 0;
+#pragma unroll
+  for (int c = 0; c < MAXCAP; ++c) P.cp[c] = c < n_cap ? tab[(F_CAP0 + c) * cap + li] : 0;
+  P.cn = n_cap > 0 ? (uint32_t)tab[F_CAPNULL * cap + li] : 0u;
+}
+
+// the page's live lanes, compacted, at entries at .. of the table; entries past `cap` are not stored.
+// Returns the live count
+template <int S>
+__device__ __forceinline__ int page_store(int64_t* tab, int cap, int64_t at, int n_cap, const PSet& P) {
+  const bool lv = P.st >= 0;
+  const uint64_t m = __ballot(lv);
+  const int64_t li = at + wave_mbcnt(m);
+  if (lv && li < cap) {
+    tab[F_STATE * cap + li] = P.st;
+    tab[F_TS0 * cap + li] = P.ts0;
+#pragma unroll
+    for (int s = 0; s < S - 1; ++s) tab[(F_SEQ0 + s) * cap + li] = P.sq[s];
+#pragma unroll
+    for (int c = 0; c < MAXCAP; ++c)
+      if (c < n_cap) tab[(F_CAP0 + c) * cap + li] = P.cp[c];
+    if (n_cap > 0) tab[F_CAPNULL * cap + li] = P.cn;
+  }
+  return __popcll(m);
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
+  static_assert(S >= 2, "a one-state chain holds no partials");
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int wid = blockIdx.x * 4 + wv;
+  if (wid >= L.n_work) return;
+  const WorkItem W = L.work[wid];
+  const ChainQuery* __restrict__ Q = L.queries + W.q;
+  const int stream = L.b.stream;
+  const int pcap = L.pcap;
+  // ---- wave-uniform program, resolved into SGPRs for the whole chunk (as nfa_chain_kernel) ----
+  const int64_t within = Q->within < 0 ? INT64_MAX : Q->within;
+  const int every = Q->every, n_cap = Q->n_cap, qid = Q->qid, n_col = Q->n_col;
+  StateDesc D[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    StateDesc d{};
+    d.active = Q->state_stream[s] == stream;
+    d.has_x = Q->xa_count[s] > 0;
+    if (d.has_x) {
+      const Atom& A = Q->atoms[Q->xa_atom[Q->xa_first[s]]];
+      d.l_cap = A.lk == OPK_CAP; d.r_cap = A.rk == OPK_CAP;
+      d.l_cur = A.lk == OPK_CUR; d.r_cur = A.rk == OPK_CUR;
+      d.lcap = d.l_cap ? A.li : 0; d.rcap = d.r_cap ? A.ri : 0;
+      d.lc = A.lc; d.rc = A.rc;
+      d.l_null = A.lk == OPK_NULL; d.r_null = A.rk == OPK_NULL;
+      d.f64 = A.f64; d.mask = A.mask;
+    }
+    uint32_t cm = 0;
+    for (int c = 0; c < n_cap; ++c) cm |= (Q->cap_slot[c] == s ? 1u : 0u) << c;
+    d.capmask = cm;
+    D[s] = d;
+  }
+
+  bool any_active = false;  // a non-start state reads this launch's stream
+#pragma unroll
+  for (int s = 1; s < S; ++s) any_active = any_active || D[s].active;
+
+  int64_t w0 = 0;
+  if (W.chunk > 0) w0 = lower_bound_ts(L.b.ts, W.c0, L.b.ts[W.c0 - 1] - within, lane);
+  // the working table: the query's next persisted table (last chunk), or the item's scratch one. The
+  // first tile of an item continuing the persisted state (w0 == 0) reads part[inb], which may have
+  // holes (the register forms leave them); every later tile reads the working table, which has none
+  const bool last_chunk = W.chunk == W.n_chunks - 1;
+  int64_t* tab = last_chunk ? L.part[1 - W.inb] + (size_t)W.q * NF * pcap : L.scratch + (size_t)W.scr * NF * pcap;
+  const int64_t* pin = L.part[W.inb] + (size_t)W.q * NF * pcap;
+  int seed_alive = w0 == 0 ? L.hdr[W.inb][W.q].seed_alive : 1;
+  int64_t nt = 0;             // entries of the working table
+  int64_t lost = 0, need = 0; // partials that found no room; the most entries (stored + lost) at a tile's end
+
+  int64_t nmatch = 0;
+  int64_t* seg = L.match + W.seg_off * L.rec_words;
+  const int RW = L.rec_words;
+  bool unordered = false, seg_over = false;
+  int64_t prev_tile_ts = (w0 == 0) ? L.b.prev_ts : L.b.ts[w0 - 1];
+
+  // (an item without events still carries the persisted table over: one pass with an empty tile)
+  bool first = true;
+  for (int64_t t = w0; first || t < W.c1; t += WAVE) {
+    // ---- stage 64 events, one per lane (as nfa_chain_kernel) ----
+    const int64_t e = t + lane;
+    const bool live = e < W.c1;
+    const int64_t ets = live ? L.b.ts[e] : INT64_MAX;
+    int64_t ck[MAXCOL];
+    uint32_t cnul = 0;
+#pragma unroll
+    for (int c = 0; c < MAXCOL; ++c) {
+      ck[c] = 0;
+      if (c < n_col && Q->col_stream[c] == stream) {
+        const int a = Q->col_attr[c];
+        uint64_t raw = 0;
+        if (live) {
+          const int wdt = L.b.width[a];
+          if (wdt == 8) raw = ((const uint64_t*)L.b.col[a])[e];
+          else if (wdt == 4) raw = ((const uint32_t*)L.b.col[a])[e];
+          else raw = ((const uint8_t*)L.b.col[a])[e];
+          if (L.b.nul[a] && ((const uint8_t*)L.b.nul[a])[e]) cnul |= 1u << c;
+        }
+        ck[c] = to_key(raw, Q->col_conv[c]);
+      }
+    }
+    // (the keys captured by value: by reference the compiler keeps ck in scratch memory here)
+    auto col_key = [ck](int col) {
+      int64_t v = ck[0];
+#pragma unroll
+      for (int c = 1; c < MAXCOL; ++c) v = (col == c) ? ck[c] : v;
+      return v;
+    };
+    uint64_t smask[S];
+    int64_t xcur[S];
+    uint32_t xnul = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      bool ok = live && D[s].active;
+      xcur[s] = 0;
+      if (D[s].active) {
+        const int a1 = Q->atom_begin[s + 1] - Q->xa_count[s];
+        for (int a = Q->atom_begin[s]; a < a1; ++a) {
+          const Atom& A = Q->atoms[a];
+          const int64_t l = A.lk == OPK_CUR ? col_key(A.li) : A.lc;
+          const int64_t r = A.rk == OPK_CUR ? col_key(A.ri) : A.rc;
+          const bool ln = A.lk == OPK_NULL || (A.lk == OPK_CUR && ((cnul >> A.li) & 1u));
+          const bool rn = A.rk == OPK_NULL || (A.rk == OPK_CUR && ((cnul >> A.ri) & 1u));
+          ok = ok && atom_eval(A, l, ln, r, rn);
+        }
+        if (D[s].has_x) {
+          const int col = Q->xa_col[Q->xa_first[s]];
+          if (col >= 0) {
+            xcur[s] = col_key(col);
+            xnul |= ((cnul >> col) & 1u) << s;
+          }
+        }
+      }
+      smask[s] = __ballot(ok);
+    }
+    int64_t capv[MAXCAP];
+    uint32_t capn = 0;
+#pragma unroll
+    for (int c = 0; c < MAXCAP; ++c) {
+      capv[c] = 0;
+      if (c < n_cap) {
+        capv[c] = col_key(Q->cap_col[c]);
+        capn |= ((cnul >> Q->cap_col[c]) & 1u) << c;
+      }
+    }
+    int64_t pred = __shfl_up(ets, 1, WAVE);
+    if (lane == 0) pred = prev_tile_ts;
+    if (live && ets < pred) unordered = true;
+    prev_tile_ts = __shfl(ets, WAVE - 1, WAVE);
+
+    const int cnt = W.c1 <= t ? 0 : (int)((W.c1 - t) < WAVE ? (W.c1 - t) : WAVE);
+
+    // the tile's events through one page, in order: the non-start body of nfa_chain_kernel at K = 1.
+    // `open` (the fresh page only): lane k's partial exists from the end of event k on
+    // (inlined at both calls: a page is registers, never an object in memory)
+    auto run_events = [&](PSet& P, const uint64_t open) __attribute__((always_inline)) {
+#pragma unroll 1
+      for (int k = 0; k < cnt; ++k) {
+        if (__ballot(P.st >= 0) == 0 && (open >> k) == 0) break;  // nothing left to examine or open
+        const int64_t j = t + k;
+        const bool emit_ok = j >= W.c0;
+        const int64_t cts = readlane64(ets, k);
+        const int64_t cseq = L.b.seq_base + j;
+        const uint32_t capn_k = __builtin_amdgcn_readlane(capn, k);
+        const uint32_t xnul_k = __builtin_amdgcn_readlane(xnul, k);
+#pragma unroll
+        for (int s = S - 1; s >= 1; --s) {
+          const StateDesc& d = D[s];
+          if (!d.active) continue;
+          const bool last = (s == S - 1);
+          const bool cpass = (smask[s] >> k) & 1ull;
+          const int64_t cur = readlane64(xcur[s], k);
+          const bool curn = (xnul_k >> s) & 1u;
+          const bool in_s = P.st == s;
+          if (__ballot(in_s) == 0) continue;
+          const bool exp = in_s && expired(P.ts0, cts, within);
+          bool pass = in_s && !exp && cpass;
+          if (d.has_x) {
+            const int64_t lcap = cap_get(P, d.lcap), rcap = cap_get(P, d.rcap);
+            const int64_t l = d.l_cap ? lcap : d.l_cur ? cur : d.lc;
+            const int64_t r = d.r_cap ? rcap : d.r_cur ? cur : d.rc;
+            const bool ln = d.l_null || (d.l_cur && curn) || (d.l_cap && ((P.cn >> d.lcap) & 1u));
+            const bool rn = d.r_null || (d.r_cur && curn) || (d.r_cap && ((P.cn >> d.rcap) & 1u));
+            pass = pass && !ln && !rn && cmp_keys(d.mask, d.f64, l, r);
+          }
+          if (last) {
+            const uint64_t m = __ballot(pass);
+            if (m && emit_ok) {
+              const int64_t rank = nmatch + wave_mbcnt(m);
+              if (nmatch + __popcll(m) > W.seg_cap) {
+                seg_over = true;
+              } else if (pass) {
+                int64_t* r = seg + rank * RW;
+                r[0] = qid;
+                r[1] = cts;
+#pragma unroll
+                for (int q2 = 0; q2 < S - 1; ++q2) r[2 + q2] = P.sq[q2];
+                r[2 + S - 1] = cseq;
+              }
+              nmatch += __popcll(m);
+            }
+            if (pass || exp) P.st = -1;
+          } else {
+            if (exp) P.st = -1;
+            if (pass) {
+              P.st = s + 1;
+              P.sq[s] = cseq;
+#pragma unroll
+              for (int c = 0; c < MAXCAP; ++c) {
+                const bool take = (d.capmask >> c) & 1u;
+                const int64_t v = readlane64(capv[c], k);
+                const uint32_t nb = (capn_k >> c) & 1u;
+                P.cp[c] = take ? v : P.cp[c];
+                P.cn = take ? ((P.cn & ~(1u << c)) | (nb << c)) : P.cn;
+              }
+            }
+          }
+        }
+        if (((open >> k) & 1ull) && lane == k) P.st = 1;
+      }
+    };
+
+    // ---- the live pages: load, run the tile, store back compacted. The write cursor wc never
+    //      passes the read cursor p0 (a page stores at most the 64 entries it loaded) ----
+    //      A stream that feeds no state but the start state (the A pushes of `A -> B`) examines no
+    //      partial: after the first tile has carried the table over, only the fresh pages are added
+    if (first || any_active) {
+      const int64_t* src = first ? pin : tab;
+      const int64_t n_src = first ? (w0 == 0 ? pcap : 0) : nt;
+      int64_t wc = 0;
+      for (int64_t p0 = 0; p0 < n_src; p0 += WAVE) {
+        const int64_t li = p0 + lane;
+        PSet P;
+        P.st = li < n_src ? (int)src[F_STATE * pcap + li] : -1;
+        if (__ballot(P.st >= 0) == 0) continue;
+        page_load<S>(src, pcap, (int)(li < n_src ? li : p0), n_cap, P);
+        run_events(P, 0);
+        wc += page_store<S>(tab, pcap, wc, n_cap, P);
+      }
+      nt = wc;
+    }
+
+    // ---- the fresh page: lane k holds the partial the seed opens at event k ----
+    uint64_t open = seed_alive ? smask[0] : 0;
+    if (!every && open) {  // without `every` the first match consumes the seed
+      open &= 0 - open;
+      seed_alive = 0;
+    }
+    if (open) {
+      const uint32_t cm0 = D[0].capmask;
+      PSet F;
+      F.st = -1;
+      F.ts0 = ets;
+      F.sq[0] = L.b.seq_base + e;
+#pragma unroll
+      for (int s = 1; s < MAXS - 1; ++s) F.sq[s] = 0;
+#pragma unroll
+      for (int c = 0; c < MAXCAP; ++c) F.cp[c] = ((cm0 >> c) & 1u) ? capv[c] : 0;
+      F.cn = capn & cm0;
+      if (any_active) run_events(F, open);
+      else F.st = ((open >> lane) & 1ull) ? 1 : -1;  // (no event of the tile examines them)
+      const int fresh = page_store<S>(tab, pcap, nt, n_cap, F);
+      const int64_t room = pcap - nt;
+      const int64_t kept = fresh < room ? fresh : room;
+      lost += fresh - kept;
+      nt += kept;
+    }
+    need = nt + lost > need ? nt + lost : need;
+    // the next tile's loads read what other lanes of this wave stored
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    first = false;
+  }
+
+  // ---- outputs ----
+  const uint64_t any_unordered = __ballot(unordered);
+  if (lane == 0) {
+    L.seg_count[wid] = nmatch;
+    if (lost > 0) {
+      atomicOr(&L.err[0], 1);
+      atomicMax(&L.err[3], (int)(need < INT32_MAX ? need : INT32_MAX));
+    }
+    if (any_unordered && W.n_chunks > 1) atomicOr(&L.err[1], 1);
+    if (seg_over) atomicOr(&L.err[2], 1);
+  }
+  if (last_chunk) {  // the working table is the instance's final state: free the lanes past its end
+    for (int64_t li = nt + lane; li < pcap; li += WAVE) tab[F_STATE * pcap + li] = -1;
+    if (lane == 0) {
+      InstHeader h;
+      h.seed_alive = seed_alive;
+      h.n_live = (int)nt;
+      h.overflow = lost > 0;
+      h.unordered = any_unordered != 0;
+      L.hdr[1 - W.inb][W.q] = h;
+    }
+  }
+}
+
+// table rows re-strided from old_cap to new_cap lanes (new_cap > old_cap): new lanes are free
+__global__ void chain_relayout_kernel(const int64_t* src, int64_t* dst, int64_t rows, int old_cap, int new_cap) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * new_cap) return;
+  const int64_t row = i / new_cap;
+  const int l = (int)(i - row * new_cap);
+  dst[i] = l < old_cap ? src[row * old_cap + l] : (row % NF == F_STATE ? -1 : 0);
+}
+
 }  // namespace sdh
 
 template <int S>
@@ -466,4 +819,27 @@ extern "C" hipError_t sdh_launch_chain(int n_states, int k, const sdh::ChainLaun
     case 4: return launch_s<4>(k, L, n_blocks, lds, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+// the paged form: chains of two to four states (a one-state chain holds no partials and stays on
+// sdh_launch_chain)
+extern "C" hipError_t sdh_launch_chain_paged(int n_states, const sdh::ChainLaunch* L, int n_blocks, hipStream_t s) {
+  if (n_blocks <= 0) return hipSuccess;
+  switch (n_states) {
+    case 2: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<2>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 3: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<3>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 4: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<4>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// `rows` table rows ([q][field]) of old_cap lanes each -> new_cap lanes each (K_chain table growth)
+extern "C" hipError_t sdh_chain_relayout(const int64_t* src, int64_t* dst, int64_t rows, int old_cap, int new_cap,
+                                         hipStream_t s) {
+  const int64_t n = rows * new_cap;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(sdh::chain_relayout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, rows,
+                     old_cap, new_cap);
+  return hipGetLastError();
 }

@@ -86,6 +86,8 @@ struct WorkItem {
   int64_t c0, c1;       // events of the batch whose emissions this item owns
   int64_t seg_off;      // first match record of this item's output segment
   int64_t seg_cap;      // capacity of the segment (records)
+  int64_t scr;          // paged form: the item's working table in ChainLaunch::scratch (-1: the item is
+                        //   its query's last chunk and works in part[1 - inb])
 };
 
 // persisted partial-match table of one query instance: NF fields x PCAP lanes (SoA, int64)
@@ -116,7 +118,7 @@ struct ChainLaunch {
   const ChainQuery* queries;
   const WorkItem* work;
   int32_t n_work;
-  int32_t pcap;             // partial capacity per instance (64 * K)
+  int32_t pcap;             // partial capacity per instance (register forms: 64 * K; paged: 64 * pages)
   StreamBatch b;
   InstHeader* hdr[2];       // double-buffered instance headers  [q]
   int64_t* part[2];         // double-buffered partial tables     [q][NF][pcap]
@@ -124,7 +126,10 @@ struct ChainLaunch {
   int32_t rec_words;
   int32_t pad;
   int64_t* seg_count;       // per work item: matches written
-  int32_t* err;             // [0] overflow, [1] unordered, [2] segment overflow
+  int32_t* err;             // [0] overflow, [1] unordered, [2] segment overflow, [3] paged form: the
+                            //   partials per instance an overflowing item would have needed
+  int64_t* scratch;         // paged form: working tables of the chunks that are not their query's
+                            //   last                              [slot][NF][pcap]
 };
 
 // ------------------------------------------------------------------------------------------

@@ -217,9 +217,10 @@ def columns_from_words(vals: np.ndarray, types: Sequence[int]) -> List[np.ndarra
 
 
 class HipEngine:
-    """One engine instance on one GPU."""
+    """One engine instance on one GPU. ``partials`` is sdh_config.partials_per_inst: 0 (the default) lets
+    the K_chain tables grow, a positive value is a fixed capacity with SDH_E_CAPACITY past it."""
 
-    def __init__(self, blob: bytes, device: int = 0, partials: int = 128, shard_rank: int = 0,
+    def __init__(self, blob: bytes, device: int = 0, partials: int = 0, shard_rank: int = 0,
                  shard_world: int = 1, chunk_events: int = 0, stream_types=None, flags: int = 0,
                  gen_pool_states: int = 0, gen_pool_nodes: int = 0, gen_list_cap: int = 0,
                  gen_max_keys: int = 0, debug=None, match_capacity: int = 0):
