@@ -514,6 +514,7 @@ struct sdh_engine {
   DevBuf<uint8_t> d_shtemp;
   DevBuf<uint2> d_shcm;
   DevBuf<int32_t> d_shcmn;
+  DevBuf<uint32_t> d_shbounds;           // [g][SH_BOUNDS] the groups' lane constants (ratchet_shared_carried)
   int64_t r_launches = 0;                // K_ratchet steps so far (SDH_RATCHET_SHARED_ALT)
   int64_t r_shared_pushes = 0;           // pushes whose records the shared-pops form wrote
   int64_t r_rec4_reruns = 0;             // pushes re-run with 8-B records (a rec4 distance reached 2^26)

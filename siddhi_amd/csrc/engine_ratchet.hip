@@ -372,6 +372,8 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
     e->r_blocks = (want + e->r_blk_recs - 1) / e->r_blk_recs;
   }
   e->d_rtotal.ensure(3);  // [0] device-record entries, [1] the placement total, [2] device-record bytes
+  // (the kernels roll to a fresh block when 64 entries and a side entry do not fit the open one)
+  if (e->r_blk_recs * 8 < 4 * WAVE + 8) throw Error(SDH_E_INVALID, "K_ratchet blocks smaller than one wave of records");
   bool no_place = false, no_rec4 = false;
   for (int attempt = 0; attempt < 40; ++attempt) {
     // out-of-order timestamps seen on this stream, timestamps so extreme that `ts0 + within`
@@ -591,6 +593,8 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
       S.cm = e->d_shcm.p;
       S.cm_n = e->d_shcmn.p;
       S.cs_n = e->d_shcmn.p + ng * WAVE;
+      e->d_shbounds.ensure(ng * (size_t)sdh::SH_BOUNDS);
+      S.bounds = e->d_shbounds.p;
       e->d_shtemp.ensure(sdh_ratchet_shared_temp(n) + 16);
       return S;
     };

@@ -8,6 +8,9 @@
 #ifndef SDH_RATCHET_NOSTORE
 #define SDH_RATCHET_NOSTORE 0
 #endif
+#ifndef SDH_RATCHET_MASK_CXX
+#define SDH_RATCHET_MASK_CXX 0
+#endif
 
 namespace sdh {
 
@@ -197,6 +200,29 @@ __global__ __launch_bounds__(64) void ratchet_shared_carried(RatchetLaunch L, Sh
   int64_t* __restrict__ o_ts = pick(L.ent_ts, ob);
   int64_t* __restrict__ o_sq = pick(L.ent_seq, ob);
   int64_t* __restrict__ o_ky = pick(L.ent_key, ob);
+  {
+    // the lane constants the emission kernel reads wave-uniformly (SharedLaunch::bounds)
+    const bool active = lane < G->n_lanes;
+    const int32_t w32 = !active ? -1 : within >= INT32_MAX ? INT32_MAX : (int32_t)within;
+    float flo, fhi;
+    sim_bounds(G, lane, active, flo, fhi);
+    float glo = flo, ghi = fhi;  // the group's widest bounds: a pair outside them is nobody's
+    int32_t gw = w32;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      glo = fminf(glo, __shfl_xor(glo, d, WAVE));
+      ghi = fmaxf(ghi, __shfl_xor(ghi, d, WAVE));
+      gw = max(gw, __shfl_xor(gw, d, WAVE));
+    }
+    const uint32_t flags = (wballot(active && fhi != __int_as_float(0x7f800000)) ? SHB_HI : 0u) |
+                           (wballot(active && w32 != INT32_MAX) ? SHB_AGE : 0u);
+    uint32_t* __restrict__ b = S.bounds + (size_t)W.g * SH_BOUNDS;
+    b[lane] = __float_as_uint(flo);
+    b[WAVE + lane] = __float_as_uint(fhi);
+    b[2 * WAVE + lane] = (uint32_t)w32;
+    b[3 * WAVE + lane] = lane == 0 ? __float_as_uint(glo) : lane == 1 ? __float_as_uint(ghi) : lane == 2 ? (uint32_t)gw
+                         : lane == 3 ? flags : 0u;
+  }
   const int64_t t_last = L.b.ts[S.n - 1];
   int nm = 0, c = n_in - 1, aged = 0, d4 = 0;
   int64_t from = 0;
@@ -238,38 +264,109 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
   return __builtin_amdgcn_readfirstlane(v);
 }
 
-// Emission: one wave per item (group x range of e2 events) filters the item's pairs, 64 per tile, and
-// writes rec4 blocks as nfa_ratchet_kernel's PM 4 does (same block machinery). The group's carried
-// matches, per lane by ascending e2, are merged in by their least pending e2 (wave-uniform). The
-// group's last item writes the next deques: the carried survivors are in place, U follows.
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const int o = __shfl_up(v, d, WAVE);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+__device__ __forceinline__ uint64_t below64(int k) { return k >= 64 ? ~0ull : (1ull << k) - 1; }  // bits < k
+
+// entries of a wave's LDS staging window (4 B each; a multiple of 4)
+#ifndef SDH_RATCHET_WIN
+#define SDH_RATCHET_WIN 2048
+#endif
+
+// The take masks of two tiles: lane k holds one pair of each tile (key, age), bit p of T says that
+// pattern p of the group takes it. The patterns' constants are lane reads of the group's bounds rows
+// (vlo, vhi, vw: lane p holds pattern p's), each used for both tiles; walking p downwards,
+// `m + m + take` inserts one bit per step.
+// HI / AGE: some pattern has a finite upper bound / a `within` (otherwise the compare is dropped).
+template <bool HI, bool AGE>
+__device__ __forceinline__ void sh_take_masks(uint32_t vlo, uint32_t vhi, uint32_t vw, float k0, int32_t a0, float k1,
+                                              int32_t a1, uint64_t& T0, uint64_t& T1) {
+  // (written out: left to itself the compiler keeps the 128 compare results in scalar registers,
+  // spills them to lanes and materialises each bit with a select and an or. SDH_RATCHET_MASK_CXX=1
+  // builds the plain C++ step instead, to measure the two against each other: DESIGN.md §3.1)
+  asm volatile("" : "+v"(vlo), "+v"(vhi), "+v"(vw));  // (the lane reads stay inside the caller's loop)
+  uint32_t m0[2] = {0, 0}, m1[2] = {0, 0};
+  uint64_t tmp;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int p = 31; p >= 0; --p) {
+      const int q = h * 32 + p;
+      const float lo = __uint_as_float(__builtin_amdgcn_readlane(vlo, q));
+      const float hi = HI ? __uint_as_float(__builtin_amdgcn_readlane(vhi, q)) : 0.f;
+      const int32_t w = AGE ? (int32_t)__builtin_amdgcn_readlane(vw, q) : 0;
+#define SH_STEP(M, K, A)                                                                                       \
+  if (HI && AGE)                                                                                               \
+    asm("v_cmp_le_f32 vcc, %[lo], %[k]\n\tv_cmp_ge_f32 %[t], %[hi], %[k]\n\ts_and_b64 vcc, vcc, %[t]\n\t"      \
+        "v_cmp_ge_i32 %[t], %[w], %[a]\n\ts_and_b64 vcc, vcc, %[t]\n\tv_addc_co_u32 %[m], vcc, %[m], %[m], vcc" \
+        : [m] "+v"(M), [t] "=&s"(tmp) : [lo] "s"(lo), [hi] "s"(hi), [w] "s"(w), [k] "v"(K), [a] "v"(A) : "vcc"); \
+  else if (HI)                                                                                                 \
+    asm("v_cmp_le_f32 vcc, %[lo], %[k]\n\tv_cmp_ge_f32 %[t], %[hi], %[k]\n\ts_and_b64 vcc, vcc, %[t]\n\t"      \
+        "v_addc_co_u32 %[m], vcc, %[m], %[m], vcc"                                                             \
+        : [m] "+v"(M), [t] "=&s"(tmp) : [lo] "s"(lo), [hi] "s"(hi), [k] "v"(K) : "vcc");                        \
+  else if (AGE)                                                                                                \
+    asm("v_cmp_le_f32 vcc, %[lo], %[k]\n\tv_cmp_ge_i32 %[t], %[w], %[a]\n\ts_and_b64 vcc, vcc, %[t]\n\t"       \
+        "v_addc_co_u32 %[m], vcc, %[m], %[m], vcc"                                                             \
+        : [m] "+v"(M), [t] "=&s"(tmp) : [lo] "s"(lo), [w] "s"(w), [k] "v"(K), [a] "v"(A) : "vcc");              \
+  else                                                                                                         \
+    asm("v_cmp_le_f32 vcc, %[lo], %[k]\n\tv_addc_co_u32 %[m], vcc, %[m], %[m], vcc"                            \
+        : [m] "+v"(M) : [lo] "s"(lo), [k] "v"(K) : "vcc")
+#if SDH_RATCHET_MASK_CXX
+      m0[h] = m0[h] + m0[h] + ((k0 >= lo && (!HI || k0 <= hi) && (!AGE || a0 <= w)) ? 1u : 0u);
+      m1[h] = m1[h] + m1[h] + ((k1 >= lo && (!HI || k1 <= hi) && (!AGE || a1 <= w)) ? 1u : 0u);
+#else
+      SH_STEP(m0[h], k0, a0);
+      SH_STEP(m1[h], k1, a1);
+#endif
+#undef SH_STEP
+    }
+  }
+  (void)tmp;
+  T0 = ((uint64_t)m0[1] << 32) | m0[0];
+  T1 = ((uint64_t)m1[1] << 32) | m1[0];
+}
+
+// Emission: one wave per item (group x range of e2 events) writes rec4 blocks (the block machinery of
+// nfa_ratchet_kernel's PM 4). First the group's carried matches at the item's events, lane = pattern,
+// by ascending e2. Then the item's pairs, 64 per tile with lane = pair: the take mask of each pair
+// over the group's patterns (sh_take_masks), the pairs' entry counts scanned into offsets, one side
+// entry per event and block from two ballots, the entries scattered through an LDS window and
+// copied to the block in whole-wave contiguous stores. A tile that does not fit the block is cut at
+// the last pair that does. The group's last item writes the next deques: the carried survivors are
+// in place, U follows.
 __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L, SharedLaunch S) {
+  __shared__ __attribute__((aligned(16))) uint32_t win[SDH_RATCHET_WIN];
+  constexpr int SH_PASS = SDH_RATCHET_WIN - 4;  // entries per pass through the window (4 slots of alignment slack)
   const int lane = threadIdx.x;
   const int wid = blockIdx.x;
   if (wid >= L.n_items) return;
   const RatchetItem W = L.items[wid];
   const RatchetGroup* __restrict__ G = L.groups + W.g;
-  const bool active = lane < G->n_lanes;
+  const uint32_t* __restrict__ bt = S.bounds + (size_t)W.g * SH_BOUNDS;  // (written by ratchet_shared_carried)
   const int64_t within = G->within[lane];
-  const int32_t w32 = !active ? -1 : within >= INT32_MAX ? INT32_MAX : (int32_t)within;
-  float flo, fhi;
-  sim_bounds(G, lane, active, flo, fhi);
-  // the group's widest bounds: a pair outside them is nobody's
-  float glo = flo, ghi = fhi;
-  int32_t gw = w32;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    glo = fminf(glo, __shfl_xor(glo, d, WAVE));
-    ghi = fmaxf(ghi, __shfl_xor(ghi, d, WAVE));
-    gw = max(gw, __shfl_xor(gw, d, WAVE));
-  }
+  const uint32_t vlo = bt[lane], vhi = bt[WAVE + lane], vw = bt[2 * WAVE + lane];
+  const float flo = __uint_as_float(vlo), fhi = __uint_as_float(vhi);
+  const float glo = __uint_as_float(bt[3 * WAVE]), ghi = __uint_as_float(bt[3 * WAVE + 1]);
+  const int32_t gw = (int32_t)bt[3 * WAVE + 2];
+  const uint32_t gflags = bt[3 * WAVE + 3];
+  const uint64_t lanes_m = below64(G->n_lanes);  // (idle patterns take nothing)
   const size_t gb = (size_t)W.g * L.rsmax * WAVE;
   const uint32_t sb32 = (uint32_t)L.b.seq_base;
   const uint32_t c0 = (uint32_t)W.c0, c1 = (uint32_t)W.c1;  // (rec4: batches of at most 2^26 events)
 
   // ---- block state (nfa_ratchet_kernel, PM 4) ----
-  constexpr int FULL_FILL = 1 << 30;
-  int blk = -1, fill = FULL_FILL, sfill = 0, mover = 0;
-  bool new_blk = false;
+  // (cap: the bytes of the open block, 0 before the first one; cur_j: the event of the block's last
+  // side entry)
+  constexpr uint32_t NO_J = 0xffffffffu;
+  int blk = -1, fill = 0, sfill = 0, cap = 0, mover = 0;
+  uint32_t cur_j = NO_J;
   unsigned long long n_emit = 0, n_bytes = 0;
   __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(L.match, 0, 0, 0x00020000);
   auto close_blk = [&]() {
@@ -285,40 +382,42 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
   auto roll = [&]() {
     close_blk();
     sfill = 0;
-    new_blk = true;
+    cur_j = NO_J;
+    cap = L.blk_recs * 8;
     int nb = 0;
     if (lane == 0) nb = atomicAdd(L.blk_next, 1);
     nb = __builtin_amdgcn_readfirstlane(nb);
-    if (nb >= L.n_blocks) {
-      mover = 1;
-      blk = -1;
-      nb = L.n_blocks;  // (the spare block)
-    } else {
-      if (lane == 0) L.blk_group[nb] = W.g;
-      blk = nb;
-    }
+    const bool over = nb >= L.n_blocks;
+    mover |= over ? 1 : 0;
+    blk = over ? -1 : nb;
+    nb = over ? L.n_blocks : nb;  // (the spare block)
+    if (!over && lane == 0) L.blk_group[nb] = W.g;
     fill = 0;
     const uint64_t base = (uint64_t)(reinterpret_cast<char*>(L.match) + (size_t)nb * L.blk_recs * 8);
     const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)base), bhi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
     wrs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)bhi << 32) | blo), 0,
                                             __builtin_amdgcn_readfirstlane(L.blk_recs * 8), 0x00020000);
   };
-  uint32_t cur_j = 0xffffffffu;  // the event of the block's last side entry
-  // the lanes of ballot m write `val` as entries of event j
+  // the carried phase (lane = pattern): the lanes of ballot m write `val` as entries of event j. A
+  // block is left when less than a pair's worth (64 entries and a side entry) is free
   auto emit = [&](uint32_t j, bool take, uint64_t m, uint32_t val) {
-    if (fill > ((L.blk_recs * 8 - 4 * WAVE * 4 - 8 - sfill * 8) >> 2)) roll();
-    if (j != cur_j || new_blk) {  // the event's side entry (again at the head of a block it spills into)
+    // (counted here, through a convergent read: the compiler otherwise sinks the popcount into both
+    // arms of the lane-variant `take` branch, and the value merged behind that branch, and with it
+    // fill, the room test and the block's descriptor, counts as lane-variant: every store then sits
+    // in a loop over its descriptor)
+    const int n_m = __builtin_amdgcn_readfirstlane(__popcll(m));
+    if (4 * (fill + WAVE) + 8 * (sfill + 1) > cap) roll();
+    if (j != cur_j) {  // the event's side entry (again at the head of a block it spills into)
       if (lane == 0) {
         const u32x2 se = {(uint32_t)fill, j};
-        __builtin_amdgcn_raw_buffer_store_b64(se, wrs, L.blk_recs * 8 - (sfill + 1) * 8, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(se, wrs, cap - (sfill + 1) * 8, 0, 0);
       }
       ++sfill;
       cur_j = j;
-      new_blk = false;
     }
     if (take && !SDH_RATCHET_NOSTORE)
       __builtin_amdgcn_raw_buffer_store_b32(val | ((uint32_t)lane << 26), wrs, (fill + wave_mbcnt(m)) * 4, 0, 0);
-    fill += __popcll(m);
+    fill += n_m;
   };
 
   // ---- the lane's carried matches from c0 on ----
@@ -365,27 +464,113 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
     }
     return lo;
   };
-  const int64_t p0 = lower(c0), p1 = lower(c1);
-  for (int64_t t = p0; t < p1; t += WAVE) {
-    const bool live = t + lane < p1;
-    uint4 pr = make_uint4(0, 0, 0, 0);
-    if (live) pr = reinterpret_cast<const uint4*>(S.pairs)[t + lane];
-    const float pk = __uint_as_float(pr.z);
-    uint64_t cand = wballot(live && pk >= glo && pk <= ghi && (int32_t)pr.w <= gw);
-    while (cand) {
-      const int k = __builtin_ctzll(cand);
-      cand &= cand - 1;
-      const uint32_t j = __builtin_amdgcn_readlane(pr.x, k);
-      const uint32_t d = __builtin_amdgcn_readlane(pr.y, k);
-      const float key = __uint_as_float(__builtin_amdgcn_readlane(pr.z, k));
-      const int32_t age = (int32_t)__builtin_amdgcn_readlane(pr.w, k);
-      if (cmin <= j) flush_carried(j);
-      const bool take = key >= flo && key <= fhi && age <= w32;
-      const uint64_t m = wballot(take);
-      if (m) emit(j, take, m, d);
+  const int64_t p0 = rfl64(lower(c0)), p1 = rfl64(lower(c1));  // (wave-uniform, and known to be)
+  flush_carried(0xfffffffeu);  // (a phase of their own: an event may own a side entry of each phase)
+
+  // one tile: lane k holds pair k = entries {d | p << 26} of event j for the set bits p of T,
+  // ascending. Pairs are sorted by j, so an event's pairs are a run of lanes
+  const uint64_t below_k = (1ull << lane) - 1, le_k = below_k | (1ull << lane);
+  auto tile = [&](uint32_t j, uint32_t d, uint64_t T) {
+    const int c = __popcll(T);
+    const uint64_t has = wballot(c > 0);
+    if (!has) return;  // (candidates of the widest bounds, no taker: nothing is written)
+    const int incl = wave_incl_scan(c, lane), off = incl - c;
+    const uint32_t jp = (uint32_t)__shfl_up((int)j, 1, WAVE);
+    const uint64_t jdiff = wballot(lane == 0 || j != jp);  // the runs' first lanes
+    for (int a = 0;;) {  // the lanes from a on, as far as the block has room
+      const uint64_t am = ~below64(a), hm = has & am;
+      if (!hm) break;
+      const int off_a = __builtin_amdgcn_readlane(off, a);
+      // a pair opens a side entry if it has entries and no earlier pair of its run from lane a on
+      // has; the first one continues the block's last side entry if that is its event's
+      const uint64_t st = (jdiff | (1ull << a)) & le_k & am;
+      const int s = 63 - __clzll(st | 1);  // the run's first lane, a at least (lanes below a open nothing)
+      bool opens = lane >= a && c > 0 && (has & below_k & ~((1ull << s) - 1)) == 0;
+      if (lane == __builtin_ctzll(hm) && j == cur_j) opens = false;
+      const uint64_t om = wballot(opens);
+      const int rank = wave_mbcnt(om);
+      // the longest prefix [a, b) whose entries and side entries fit (the need grows with the lane)
+      const int need = 4 * (fill + incl - off_a) + 8 * (sfill + rank + (opens ? 1 : 0));
+      const uint64_t nf = wballot(need > cap) & am;
+      const int b = nf ? __builtin_ctzll(nf) : 64;
+      if (b == a) {  // (not even pair a: a fresh block holds it, launch_ratchet checks the block size)
+        roll();
+        continue;
+      }
+      const uint64_t chunk = below64(b) & am, omc = om & chunk;
+      const bool mine = (chunk >> lane) & 1;
+      const int E = (b == 64 ? __builtin_amdgcn_readlane(incl, 63) : __builtin_amdgcn_readlane(off, b)) - off_a;
+      if (opens && mine) {
+        const u32x2 se = {(uint32_t)(fill + off - off_a), j};
+        __builtin_amdgcn_raw_buffer_store_b64(se, wrs, cap - (sfill + rank + 1) * 8, 0, 0);
+      }
+      // the entries through the window: each lane writes its next entries while they lie inside the
+      // pass, low half of T first; then the wave copies the pass out. Entry 0 of the pass sits at slot
+      // fill & 3 of the window, so a 16-B-aligned quad of the window is one of the block: the middle
+      // goes out as 16-B stores (1 KiB per wave instruction), up to three entries at either end as
+      // 4-B stores
+      uint32_t rlo = mine ? (uint32_t)T : 0u, rhi = mine ? (uint32_t)(T >> 32) : 0u;
+      uint32_t pos = (uint32_t)(off - off_a);
+      const int sh = fill & 3;
+      for (int w0 = 0; w0 < E; w0 += SH_PASS) {
+        uint32_t idx = pos - (uint32_t)w0;  // (beyond the pass for a lane whose entries start later)
+        while (rlo != 0 && idx < (uint32_t)SH_PASS) {
+          win[sh + idx] = d | ((uint32_t)__builtin_ctz(rlo) << 26);
+          rlo &= rlo - 1;
+          ++idx;
+        }
+        while (rlo == 0 && rhi != 0 && idx < (uint32_t)SH_PASS) {
+          win[sh + idx] = d | ((32u + (uint32_t)__builtin_ctz(rhi)) << 26);
+          rhi &= rhi - 1;
+          ++idx;
+        }
+        pos = (uint32_t)w0 + idx;
+        __syncthreads();
+        const int n = min(SH_PASS, E - w0), g0 = fill + w0;  // (g0 - sh is a multiple of 4)
+        const int nh = min(n, (4 - sh) & 3), nq = (n - nh) >> 2, nt = n - nh - 4 * nq;
+        if (lane < nh + nt) {
+          const int e = lane < nh ? lane : 4 * nq + lane;
+          const uint32_t v = win[sh + e];
+          if (!SDH_RATCHET_NOSTORE) __builtin_amdgcn_raw_buffer_store_b32(v, wrs, (g0 + e) * 4, 0, 0);
+        }
+        for (int q0 = 0; q0 < nq; q0 += WAVE) {
+          const int q = q0 + lane;
+          if (q < nq) {
+            const u32x4 v = reinterpret_cast<const u32x4*>(win)[((sh + nh) >> 2) + q];  // (sh + nh is 0 or 4)
+            if (!SDH_RATCHET_NOSTORE) __builtin_amdgcn_raw_buffer_store_b128(v, wrs, (g0 + nh + 4 * q) * 4, 0, 0);
+          }
+        }
+        __syncthreads();
+      }
+      fill += E;
+      sfill += __builtin_amdgcn_readfirstlane(__popcll(omc));
+      if (omc) cur_j = __builtin_amdgcn_readlane(j, 63 - __clzll(omc));
+      if (b == 64) break;
+      roll();
+      a = b;
     }
+  };
+
+  // ---- the item's pairs, two tiles per read of the group's constants ----
+  for (int64_t t = p0; t < p1; t += 2 * WAVE) {
+    const bool live0 = t + lane < p1, live1 = t + WAVE + lane < p1;
+    uint4 pr0 = make_uint4(0, 0, 0, 0), pr1 = pr0;
+    if (live0) pr0 = reinterpret_cast<const uint4*>(S.pairs)[t + lane];
+    if (live1) pr1 = reinterpret_cast<const uint4*>(S.pairs)[t + WAVE + lane];
+    const float k0 = __uint_as_float(pr0.z), k1 = __uint_as_float(pr1.z);
+    const int32_t a0 = (int32_t)pr0.w, a1 = (int32_t)pr1.w;
+    const bool cand0 = live0 && k0 >= glo && k0 <= ghi && a0 <= gw, cand1 = live1 && k1 >= glo && k1 <= ghi && a1 <= gw;
+    if (wballot(cand0 || cand1) == 0) continue;  // outside the group's widest bounds: nobody's
+    uint64_t T0, T1;
+    if (gflags == 0) sh_take_masks<false, false>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    else if (gflags == SHB_AGE) sh_take_masks<false, true>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    else if (gflags == SHB_HI) sh_take_masks<true, false>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    else sh_take_masks<true, true>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    T0 = cand0 ? T0 & lanes_m : 0;
+    T1 = cand1 ? T1 & lanes_m : 0;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) tile(h ? pr1.x : pr0.x, h ? pr1.y : pr0.y, h ? T1 : T0);
   }
-  flush_carried(0xfffffffeu);
   close_blk();
 
   int overflow = 0;

@@ -277,7 +277,14 @@ struct SharedLaunch {
   uint2* cm;
   int32_t* cm_n;
   int32_t* cs_n;
+  // the groups' lane constants, [g][SH_BOUNDS] words written by ratchet_shared_carried for the emission
+  // kernel's wave-uniform reads: rows of 64 {flo bits}, {fhi bits}, {w32} (sim_bounds; the 32-bit
+  // `within`, -1 for idle lanes), then {glo bits, ghi bits, gw, flags}: the group's widest bounds and
+  // SHB_HI (an active lane's fhi is finite) | SHB_AGE (an active lane has a `within`)
+  uint32_t* bounds;
 };
+constexpr int SH_BOUNDS = 4 * 64;
+constexpr uint32_t SHB_HI = 1, SHB_AGE = 2;
 
 // ------------------------------------------------------------------------------------------
 // K_gen launch (nfa_gen.hip): item = (segment of one key's events, group of 64 queries)
