@@ -20,6 +20,10 @@
  *                          chains (the StateEvent contents of StateEvent.java:138-182)
  *   sdh_engine_poll_records the matches as the kernels wrote them, left in HBM for a device consumer
  *                          (SDH_FLAG_DEVICE_MATCHES; the formats are documented below)
+ *   sdh_engine_retain_events / sdh_engine_poll_rows / sdh_engine_query_outputs
+ *                       <- query/selector/QuerySelector.java:76-169 (process: the `select` list evaluated
+ *                          over each completed StateEvent): the output rows, projected on the device from
+ *                          an event store in HBM
  *   sdh_engine_set_strings  <- partition/PartitionStreamReceiver.java:277-281 (String.valueOf of a
  *                          string key: its hashCode / length, for the fan-out order)
  *   sdh_engine_reserve / sdh_engine_reserve_keys
@@ -247,6 +251,42 @@ typedef struct sdh_matches_compact_ex {
   const int32_t* chain;
 } sdh_matches_compact_ex;
 int sdh_engine_poll_compact_ex(sdh_engine* e, int32_t device, sdh_matches_compact_ex* out);
+/* ---- Output rows (QuerySelector.process, query/selector/QuerySelector.java:76-169) ----
+ * sdh_engine_retain_events: keep the last `events` pushed events (rounded up to a power of two, cap) in
+ * HBM, so that sdh_engine_poll_rows can read the attributes a `select` list names. Off by default: an
+ * engine that never calls it keeps no events and does no work for them. A later call with a larger
+ * value grows the store and keeps its contents; a smaller one changes nothing. Events pushed before the
+ * first call are not kept. The store is a row-major ring indexed by sequence number: event seq is row
+ * seq & (cap - 1) of W = 2 + (the most attributes any stream has) int64 words
+ * {ts, null bits (bit a: attribute a is null), attribute 0, 1, ...}, each attribute as its raw 64-bit
+ * word: int / long sign-extended, float bits in the low 32 bits (high bits zero), double bits, bool
+ * 0 / 1, string dictionary id. events <= 0: SDH_E_INVALID.
+ *
+ * sdh_engine_poll_rows: the matches sdh_engine_poll would return, in its order, each projected through
+ * its query's `select` list into one row of `width` cells (aggregations, group by and having are not on
+ * this path: such apps are refused when they are planned). cells is column-major, cells[c * n + i] =
+ * cell c of row i in the encoding above (0 under a null); bit c of nulls[i] is set when that cell is
+ * null or c >= the number of outputs of query[i] (bits up to 63 alike). The window is consumed on
+ * success only. Failures: SDH_E_INVALID without a prior sdh_engine_retain_events; SDH_E_UNSUPPORTED when
+ * a query selects more than 64 outputs; SDH_E_CAPACITY when a match names an event that has left the
+ * store -- raise sdh_engine_retain_events; the matches stay pending and sdh_engine_poll still returns
+ * them. device != 0 leaves every array in engine-owned HBM (valid until the next push / poll /
+ * destroy); otherwise they are engine-owned host buffers. With SDH_FLAG_DEVICE_MATCHES n is 0, as for
+ * the other polls. */
+typedef struct sdh_rows {
+  int64_t n;              /* rows, in sdh_engine_poll's order                         */
+  int32_t width;          /* cells per row: the most outputs any query has            */
+  int32_t flags;          /* 0                                                        */
+  const int32_t* query;   /* [n]                                                      */
+  const int64_t* ts;      /* [n] output event timestamp (sdh_matches.ts)              */
+  const int64_t* seq;     /* [n] sdh_matches.seq                                      */
+  const int64_t* cells;   /* [width][n]: cells[c * n + i], raw 64-bit attribute words */
+  const uint64_t* nulls;  /* [n] bit c: cell c is null or beyond the query's outputs  */
+} sdh_rows;
+int sdh_engine_retain_events(sdh_engine* e, int64_t events);
+int sdh_engine_poll_rows(sdh_engine* e, int32_t device, sdh_rows* out);
+/* n_out and the SDH_T_* type (siddhi_hip_ir.h) of each output of `query` (types may be NULL; cap entries) */
+int sdh_engine_query_outputs(sdh_engine* e, int32_t query, int32_t* n_out, int32_t* types, int32_t cap);
 /* Device-resident match count of the last push (no host copy of the matches). */
 int sdh_engine_pending_matches(sdh_engine* e, int64_t* n);
 /* ---- Device records (SDH_FLAG_DEVICE_MATCHES) ----

@@ -346,6 +346,163 @@ void d2h_sync(sdh_engine* e, void* dst, const void* src, size_t bytes) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Event store and device selector (select.hip): sdh_engine_retain_events / sdh_engine_poll_rows
+// ------------------------------------------------------------------------------------------
+void check_usable(sdh_engine* e);
+
+template <class T>
+void upload(DevBuf<T>& d, const std::vector<T>& v) {
+  d.ensure(std::max<size_t>(1, v.size()));
+  if (!v.empty()) HIPCHK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+}
+
+// the select lists lowered (host only; sdh_engine_query_outputs needs no more)
+void sel_lower(sdh_engine* e) {
+  if (e->sel_ready) return;
+  e->selp = lower_outputs(e->lp);
+  e->sel_ready = true;
+}
+
+// the batch's events into the store, rows by seq (a batch longer than the ring: its last ev_cap events)
+void store_append(sdh_engine* e, StreamBatch B, const std::vector<int>& types) {
+  if (B.n > e->ev_cap) {
+    const int64_t skip = B.n - e->ev_cap;
+    B.ts += skip;
+    for (int a = 0; a < B.n_attr; ++a) {
+      B.col[a] = (const uint8_t*)B.col[a] + skip * B.width[a];
+      if (B.nul[a]) B.nul[a] += skip;
+    }
+    B.seq_base += skip;
+    B.n = e->ev_cap;
+  }
+  uint32_t fm = 0;
+  for (int a = 0; a < B.n_attr; ++a)
+    if (types[a] == T_FLOAT) fm |= 1u << a;
+  HIPCHK(sdh_store_append(&B, fm, e->ev_rows.p, e->ev_cap - 1, e->ev_w, e->stream));
+}
+
+int do_retain(sdh_engine* e, int64_t events) {
+  check_usable(e);
+  HIPCHK(hipSetDevice(e->dev));
+  if (events > ((int64_t)1 << 40)) throw Error(SDH_E_INVALID, "sdh_engine_retain_events: more than 2^40 events");
+  int64_t cap = 1;
+  while (cap < events) cap <<= 1;
+  if (e->ev_cap == 0) {
+    sel_lower(e);
+    upload(e->d_sel_code, e->selp.code);
+    upload(e->d_sel_outs, e->selp.outs);
+    upload(e->d_sel_shapes, e->selp.shapes);
+    upload(e->d_sel_queries, e->selp.queries);
+    upload(e->d_sel_consts, e->selp.consts);
+    size_t na = 0;
+    for (const auto& s : e->prog.stream_types) na = std::max(na, s.size());
+    e->ev_w = 2 + (int)na;
+    e->ev_first = e->seq;  // events pushed before this call were not kept
+  }
+  if (cap <= e->ev_cap) return SDH_OK;
+  // a larger ring: the present rows move to their places in it
+  int64_t* q = nullptr;
+  const size_t bytes = (size_t)cap * e->ev_w * 8;
+  alloc_trace("event_store", bytes);
+  if (hipMalloc(&q, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    throw Error(SDH_E_CAPACITY, fmt("device memory exhausted for an event store of %lld events", (long long)cap));
+  }
+  if (e->ev_cap) {
+    const int64_t lo = std::max(e->ev_first, e->seq - e->ev_cap);
+    hipError_t rc = sdh_store_relay(e->ev_rows.p, e->ev_cap - 1, q, cap - 1, e->ev_w, lo, e->seq - lo, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);
+    if (rc != hipSuccess) {
+      (void)hipFree(q);
+      HIPCHK(rc);
+    }
+    e->ev_first = lo;
+    HIPCHK(hipFree(e->ev_rows.p));
+  }
+  e->ev_rows.p = q;
+  e->ev_rows.n = (size_t)cap * e->ev_w;
+  e->ev_cap = cap;
+  return SDH_OK;
+}
+
+// sdh_engine_poll_rows: the window's matches projected into output rows. A sorted window goes through
+// table_order's permutation, a placed one is read from its compact rows: neither is expanded into the
+// other. An event that has left the store fails the call with the window left pending (the convention
+// of do_poll_compact for rows it cannot express).
+int do_poll_rows(sdh_engine* e, sdh_rows* out, bool device) {
+  check_usable(e);
+  if (!e->ev_cap) throw Error(SDH_E_INVALID, "sdh_engine_poll_rows: no events are kept (sdh_engine_retain_events)");
+  const auto& S = e->selp;
+  if (S.over >= 0)
+    throw Error(SDH_E_UNSUPPORTED, fmt("query %d selects more than %d outputs", S.over, sel::MAXOUT));
+  if (S.bad) throw Error(SDH_E_INVALID, "a select list names a slot or an attribute its query lacks");
+  if (S.max_depth > kg::GSTACK - 1)
+    throw Error(SDH_E_UNSUPPORTED, "a select expression is too deep for the device evaluation stack");
+  HIPCHK(hipSetDevice(e->dev));
+  const int64_t n = e->mt.n;
+  const int width = S.width;
+  const size_t rows = (size_t)std::max<int64_t>(n, POLL_MIN_ROWS);
+  e->pr_q.ensure(rows);
+  e->pr_nulls.ensure(rows);
+  e->pr_cells.ensure(rows * (size_t)std::max(1, width));
+  e->pr_err.ensure(1);
+  poll_reserve(e, n, 0);
+  if (n) {
+    const sel::Tables T{e->d_sel_code.p, e->d_sel_outs.p, e->d_sel_shapes.p, e->d_sel_queries.p, e->d_sel_consts.p};
+    const sel::Store st{e->ev_rows.p, e->ev_cap - 1, std::max(e->ev_first, e->seq - e->ev_cap), e->ev_w, 0};
+    const int deep = S.max_depth > kg::RSTACK;
+    HIPCHK(hipMemsetAsync(e->pr_err.p, 0, 4, e->stream));
+    if (e->mt.placed) {
+      HIPCHK(sdh_select_placed(&T, &st, deep, e->pc_rows.p, e->cw, e->ts_log.p, e->seq_ref, n, width, e->pr_q.p,
+                               e->po_ts.p, e->po_seq.p, e->pr_cells.p, e->pr_nulls.p, e->pr_err.p, e->stream));
+    } else {
+      int64_t tw = 0;
+      const int32_t* perm = table_order(e, &tw);
+      HIPCHK(sdh_select_sorted(&T, &st, deep, table_view(e), perm, e->po_q.p, n, width, e->pr_q.p, e->pr_cells.p,
+                               e->pr_nulls.p, e->pr_err.p, e->stream));
+    }
+    int32_t bad = 0;
+    d2h_sync(e, &bad, e->pr_err.p, 4);
+    if (bad)
+      throw Error(SDH_E_CAPACITY, fmt("a match reads an event that has left the event store of %lld events: raise "
+                                      "sdh_engine_retain_events (the matches stay pending: sdh_engine_poll)",
+                                      (long long)e->ev_cap));
+  }
+  out->n = n;
+  out->width = width;
+  out->flags = 0;
+  if (device) {
+    out->query = e->pr_q.p;
+    out->ts = e->po_ts.p;
+    out->seq = e->po_seq.p;
+    out->cells = e->pr_cells.p;
+    out->nulls = e->pr_nulls.p;
+  } else {
+    e->hr_q.ensure(rows);
+    e->ho_ts.ensure(rows);
+    e->ho_seq.ensure(rows);
+    e->hr_nulls.ensure(rows);
+    e->hr_cells.ensure(rows * (size_t)std::max(1, width));
+    if (n) {
+      HIPCHK(hipMemcpyAsync(e->hr_q.p, e->pr_q.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->ho_ts.p, e->po_ts.p, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->ho_seq.p, e->po_seq.p, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->hr_nulls.p, e->pr_nulls.p, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+      if (width)
+        HIPCHK(hipMemcpyAsync(e->hr_cells.p, e->pr_cells.p, (size_t)n * width * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    out->query = e->hr_q.p;
+    out->ts = e->ho_ts.p;
+    out->seq = e->ho_seq.p;
+    out->cells = e->hr_cells.p;
+    out->nulls = e->hr_nulls.p;
+  }
+  table_clear(e);
+  return SDH_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // K_gen host side: lowering, instance arenas, partition routing, launch, match collection
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
@@ -1663,6 +1820,7 @@ int do_push(sdh_engine* e, int32_t stream, const sdh_batch* b) {
   } else {
     stage_host_batch(e, b, B);
   }
+  if (e->ev_cap) store_append(e, B, types);
   std::vector<int> qs;
   for (int li = 0; li < (int)e->lq.size(); ++li)
     if (std::find(e->lq[li].streams.begin(), e->lq[li].streams.end(), stream) != e->lq[li].streams.end())
@@ -2656,6 +2814,29 @@ int sdh_engine_poll_compact(sdh_engine* e, int32_t device, sdh_matches_compact* 
   return guard(e, [&]() { return do_poll_compact(e, out, device != 0); });
 }
 
+int sdh_engine_retain_events(sdh_engine* e, int64_t events) {
+  if (!e || events <= 0) return SDH_E_INVALID;
+  return guard(e, [&]() { return do_retain(e, events); });
+}
+
+int sdh_engine_poll_rows(sdh_engine* e, int32_t device, sdh_rows* out) {
+  if (!e || !out) return SDH_E_INVALID;
+  return guard(e, [&]() { return do_poll_rows(e, out, device != 0); });
+}
+
+int sdh_engine_query_outputs(sdh_engine* e, int32_t query, int32_t* n_out, int32_t* types, int32_t cap) {
+  if (!e || !n_out || cap < 0) return SDH_E_INVALID;
+  return guard(e, [&]() {
+    sel_lower(e);
+    if (query < 0 || (size_t)query >= e->selp.types.size()) throw Error(SDH_E_INVALID, "no such query");
+    const size_t no = e->lp.q[(size_t)query].outs.size();
+    *n_out = (int32_t)no;
+    const auto& ty = e->selp.types[(size_t)query];
+    for (size_t c = 0; types && c < ty.size() && c < (size_t)cap; ++c) types[c] = ty[c];
+    return SDH_OK;
+  });
+}
+
 // keys a partition has seen so far (its routing table's dense ids)
 int64_t route_keys(sdh_engine* e, int partition) {
   if (partition < 0 || partition >= (int)e->routes.size() || !e->routes[partition]) return 0;
@@ -2865,6 +3046,7 @@ int sdh_engine_stats(sdh_engine* e, sdh_stats* out) {
 // header + table, ratchet deques, K_gen arenas + key tables, K_seq tails
 constexpr int64_t SNAP_MAGIC = 0x5344485350415254LL;
 constexpr int64_t SNAP_VERSION = 8;
+constexpr int64_t SNAP_VERSION_EVENTS = 9;  // version 8 followed by the event store (sdh_engine_retain_events)
 // Device memory of the sparse K_slab state: the live blocks' bytes, the slab's reserved bytes (live
 // blocks, not yet reclaimed superseded ones, and free room) and the directory's
 int sdh_engine_state_bytes(sdh_engine* e, int64_t* live_bytes, int64_t* reserved_bytes, int64_t* dir_bytes) {
@@ -2909,7 +3091,8 @@ int sdh_engine_snapshot(sdh_engine* e, void** blob, size_t* len) {
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t nq = e->lq.size();
     const size_t tbl = (size_t)NF * e->pcap;
-    std::vector<int64_t> w{SNAP_MAGIC, SNAP_VERSION, (int64_t)nq, e->pcap, e->gB32, e->gB64,
+    // (an engine that keeps events writes version 9: version 8 and, at the end, the event store)
+    std::vector<int64_t> w{SNAP_MAGIC, e->ev_cap ? SNAP_VERSION_EVENTS : SNAP_VERSION, (int64_t)nq, e->pcap, e->gB32, e->gB64,
                            e->gsz.R, e->gsz.N, e->gsz.LC, e->started ? 1 : 0, e->start_ts, e->seq,
                            (int64_t)e->prev_ts.size()};
     w.insert(w.end(), e->prev_ts.begin(), e->prev_ts.end());
@@ -3037,6 +3220,17 @@ int sdh_engine_snapshot(sdh_engine* e, void** blob, size_t* len) {
       put_dev(packed.p, (size_t)words * 4);
       put_dev(ss.live.p, 256 * 8);
     }
+    // the event store: cap, row words, the first retained seq, then the retained rows in seq order
+    if (e->ev_cap) {
+      const int64_t lo = std::max(e->ev_first, e->seq - e->ev_cap), n = e->seq - lo;
+      w.push_back(e->ev_cap);
+      w.push_back(e->ev_w);
+      w.push_back(lo);
+      // (the ring holds them in at most two runs: up to its end, then from its start)
+      const int64_t r0 = lo & (e->ev_cap - 1), n0 = std::min(n, e->ev_cap - r0);
+      put_dev(e->ev_rows.p + r0 * e->ev_w, (size_t)n0 * e->ev_w * 8);
+      put_dev(e->ev_rows.p, (size_t)(n - n0) * e->ev_w * 8);
+    }
     *len = w.size() * 8;
     *blob = malloc(*len);
     memcpy(*blob, w.data(), *len);
@@ -3054,7 +3248,9 @@ int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len) {
       return w[i++];
     };
     if (nx() != SNAP_MAGIC) throw Error(SDH_E_INVALID, "bad snapshot magic");
-    if (nx() != SNAP_VERSION) throw Error(SDH_E_INVALID, "snapshot of another format version");
+    const int64_t version = nx();
+    if (version != SNAP_VERSION && version != SNAP_VERSION_EVENTS)
+      throw Error(SDH_E_INVALID, "snapshot of another format version");
     const size_t nq = (size_t)nx();
     const int64_t spcap = nx();  // the snapshot's K_chain table capacity
     if (nq != e->lq.size() || spcap < 64 || spcap % 64 || spcap > (1 << 24))
@@ -3234,6 +3430,27 @@ int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len) {
         throw Error(SDH_E_CAPACITY, "K_slab restore: a ring overflowed");
       slab_heads(e, ss);
       ss.h_push0 = ss.h_head;
+    }
+    // the event store: a retaining engine takes the snapshot's retained rows (those that fit its ring);
+    // a version-8 snapshot, or an engine that keeps no events, leaves the store empty
+    e->ev_first = e->seq;
+    if (version == SNAP_VERSION_EVENTS) {
+      const int64_t scap = nx(), sw = nx(), lo = nx();
+      const int64_t n = e->seq - lo;
+      if (scap < 1 || sw < 2 || sw > 2 + MAXATTR || lo < 0 || n < 0 || n > scap ||
+          (size_t)n * (size_t)sw > nw - i)
+        throw Error(SDH_E_INVALID, "bad snapshot event store");
+      if (e->ev_cap) {
+        if (sw != e->ev_w) throw Error(SDH_E_INVALID, "snapshot of a different program");
+        const int64_t keep = std::min(n, e->ev_cap), first = e->seq - keep;
+        i += (size_t)((n - keep) * sw);
+        const int64_t r0 = first & (e->ev_cap - 1), n0 = std::min(keep, e->ev_cap - r0);
+        get_dev(e->ev_rows.p + r0 * e->ev_w, (size_t)n0 * sw * 8);
+        get_dev(e->ev_rows.p, (size_t)(keep - n0) * sw * 8);
+        e->ev_first = first;
+      } else {
+        i += (size_t)(n * sw);
+      }
     }
     e->g_dev_matches = 0;
     e->device_matches = 0;

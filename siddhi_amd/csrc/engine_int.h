@@ -31,6 +31,7 @@
 #include "knobs.h"
 #include "gen_lower.h"
 #include "nfa_types.h"
+#include "select_lower.h"
 #include "slab.h"
 
 #pragma GCC visibility push(hidden)
@@ -284,6 +285,25 @@ struct sdh_engine {
   DevBuf<int64_t> ts_log;
   HostBuf<int32_t> hc_rows;
   int cw = 4;
+  // ---- event store and device selector (select.hip; sdh_engine_retain_events / sdh_engine_poll_rows) ----
+  // ev_cap == 0: no retention, and no push does any work for it. Otherwise ev_rows is a ring of ev_cap
+  // (a power of two) rows of ev_w words indexed by seq; events [max(ev_first, seq - ev_cap), seq) are present
+  int64_t ev_cap = 0, ev_first = 0;
+  int ev_w = 2;
+  DevBuf<int64_t> ev_rows;
+  sel::Program selp;                 // the select lists, lowered (select_lower.h) at the first retain
+  bool sel_ready = false;
+  DevBuf<kg::GInsn> d_sel_code;
+  DevBuf<sel::Out> d_sel_outs;
+  DevBuf<sel::Shape> d_sel_shapes;
+  DevBuf<sel::Query> d_sel_queries;
+  DevBuf<int64_t> d_sel_consts;
+  DevBuf<int32_t> pr_q, pr_err;      // sdh_rows outputs (ts / seq share po_ts / po_seq)
+  DevBuf<int64_t> pr_cells;
+  DevBuf<uint64_t> pr_nulls;
+  HostBuf<int32_t> hr_q;
+  HostBuf<int64_t> hr_cells;
+  HostBuf<uint64_t> hr_nulls;
   // ---- K_gen (general interpreter) ----
   kg::LProgram lp;                   // full IR (receivers, runtime tree, partitions)
   std::vector<int> out_rank;         // R18 rank per (query, stream)
@@ -583,6 +603,7 @@ IProgram read_ir(const void* blob, size_t len);
 Lowered lower_query(const IProgram& P, int qi);
 int attr_width(int t);
 RatchetPlan ratchet_plan(const ChainQuery& c);
+sel::Program lower_outputs(const kg::LProgram& P);
 // engine_ratchet.hip
 void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
             const std::vector<int>& qs, bool allow_chunks, bool* unordered);

@@ -83,7 +83,7 @@ IProgram read_ir(const void* blob, size_t len) {
     n = r.next();
     for (int64_t k = 0; k < n * 4; ++k) r.next();        // runtime tree
     n = r.next();
-    for (int64_t k = 0; k < n; ++k) read_code(r);        // selector outputs (host-side projection)
+    for (int64_t k = 0; k < n; ++k) read_code(r);        // selector outputs (kg::read_program keeps them)
   }
   return p;  // partitions follow; partitioned queries are rejected by the lowering below
 }
@@ -294,6 +294,13 @@ Lowered lower_query(const IProgram& P, int qi) {
   L.ok = true;
   return L;
 }
+
+// ------------------------------------------------------------------------------------------
+// lowering: the queries' `select` lists -> the device selector's tables (select_lower.h): per query
+// n_out, per output its code range and result type, the instructions in one table; shapes
+// deduplicated, CONST immediates per query, single-OP_ATTR outputs marked for the direct load
+// ------------------------------------------------------------------------------------------
+sel::Program lower_outputs(const kg::LProgram& P) { return sel::lower_select(P); }
 
 int attr_width(int t) {
   switch (t) {

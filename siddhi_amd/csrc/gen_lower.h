@@ -42,6 +42,7 @@ struct LQuery {
   std::vector<int> start_ids;
   std::vector<LRecv> recvs;
   std::vector<LNode> nodes;
+  std::vector<LCode> outs;  // the `select` list: one program per output attribute (select_lower.h)
 };
 struct LPartKey {
   int stream;
@@ -138,7 +139,9 @@ inline LProgram read_program(const void* blob, size_t len) {
       d.type = (int)nx(); d.a = (int)nx(); d.b = (int)nx(); d.pre = (int)nx();
     }
     const int64_t no = nx();
-    for (int64_t k = 0; k < no; ++k) code();
+    if (no < 0 || (size_t)no > n - i) throw LowerError("IR blob truncated");
+    q.outs.resize((size_t)no);
+    for (auto& o : q.outs) o = code();
   }
   p.parts.resize((size_t)nx());
   for (auto& pd : p.parts) {

@@ -347,11 +347,12 @@ KG_UNROLL
 
 // imm(pc): the lane's constant of CONST instruction pc (its own query's, or its column of a
 // lane-interleaved constant table: kg::LaneConsts)
+// (eval_insns_imm: over an instruction table; the selector's programs are not part of a GQuery)
 template <class Stack = ArrStack, class Imm, class Attr, class StreamNull>
-KG_FN Val eval_code_imm(const GQuery* q, Imm imm_of, int b, int e, Attr attr, StreamNull stream_null) {
+KG_FN Val eval_insns_imm(const GInsn* code, Imm imm_of, int b, int e, Attr attr, StreamNull stream_null) {
   Stack stk;
   for (int pc = b; pc < e; ++pc) {
-    const GInsn& in = q->code[pc];
+    const GInsn& in = code[pc];
     switch (in.op) {
       case OP_CONST: {  // constants differ within a shape: the lane's own query
         const int64_t imm = imm_of(pc);
@@ -409,6 +410,10 @@ KG_FN Val eval_code_imm(const GQuery* q, Imm imm_of, int b, int e, Attr attr, St
     }
   }
   return stk.result();
+}
+template <class Stack = ArrStack, class Imm, class Attr, class StreamNull>
+KG_FN Val eval_code_imm(const GQuery* q, Imm imm_of, int b, int e, Attr attr, StreamNull stream_null) {
+  return eval_insns_imm<Stack>(q->code, imm_of, b, e, attr, stream_null);
 }
 
 template <class Stack = ArrStack, class Attr, class StreamNull>

@@ -24,7 +24,25 @@ namespace kg {
 struct GLayout;
 struct GQuery;
 }  // namespace kg
+namespace sel {
+struct Tables;
+struct Store;
+}  // namespace sel
 }  // namespace sdh
+
+// the event store and the device selector (select.hip)
+extern "C" hipError_t sdh_store_append(const sdh::StreamBatch* B, uint32_t float_mask, int64_t* rows, int64_t mask,
+                                       int W, hipStream_t s);
+extern "C" hipError_t sdh_store_relay(const int64_t* src, int64_t src_mask, int64_t* dst, int64_t dst_mask, int W,
+                                      int64_t lo, int64_t n, hipStream_t s);
+extern "C" hipError_t sdh_select_sorted(const sdh::sel::Tables* T, const sdh::sel::Store* st, int deep,
+                                        sdh::MatchTable M, const int32_t* perm, const int64_t* po_q, int64_t n,
+                                        int width, int32_t* oq, int64_t* cells, uint64_t* nulls, int32_t* err,
+                                        hipStream_t s);
+extern "C" hipError_t sdh_select_placed(const sdh::sel::Tables* T, const sdh::sel::Store* st, int deep,
+                                        const int32_t* crow, int cw, const int64_t* ts_log, int64_t seq_ref, int64_t n,
+                                        int width, int32_t* oq, int64_t* ots, int64_t* oseq, int64_t* cells,
+                                        uint64_t* nulls, int32_t* err, hipStream_t s);
 
 extern "C" hipError_t sdh_launch_gen(const sdh::GenLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_part(const sdh::PartLaunch* L, hipStream_t s);

@@ -90,6 +90,14 @@ class SdhMatchesCompactEx(ctypes.Structure):
                 ("n_chain", ctypes.c_int64), ("chain", ctypes.POINTER(ctypes.c_int32))]
 
 
+class SdhRows(ctypes.Structure):
+    """sdh_rows (include/siddhi_hip.h): the matches projected into output rows, column-major cells."""
+    _fields_ = [("n", ctypes.c_int64), ("width", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("query", ctypes.POINTER(ctypes.c_int32)), ("ts", ctypes.POINTER(ctypes.c_int64)),
+                ("seq", ctypes.POINTER(ctypes.c_int64)), ("cells", ctypes.POINTER(ctypes.c_int64)),
+                ("nulls", ctypes.POINTER(ctypes.c_uint64))]
+
+
 class SdhStats(ctypes.Structure):
     _fields_ = [("events", ctypes.c_int64), ("pattern_events", ctypes.c_int64),
                 ("matches", ctypes.c_int64), ("live_partials", ctypes.c_int64),
@@ -112,7 +120,8 @@ EXPORTS = ["sdh_engine_create", "sdh_engine_push", "sdh_engine_flush", "sdh_engi
            "sdh_engine_push_stats", "sdh_comm_get_id", "sdh_comm_create", "sdh_comm_create_local",
            "sdh_comm_destroy", "sdh_comm_last_error", "sdh_engine_set_comm", "sdh_engine_push_bcast",
            "sdh_engine_gather", "sdh_engine_reserve", "sdh_engine_reserve_keys", "sdh_engine_poll_records",
-           "sdh_engine_records_compact", "sdh_engine_debug_shared_pushes"]
+           "sdh_engine_records_compact", "sdh_engine_debug_shared_pushes", "sdh_engine_retain_events",
+           "sdh_engine_poll_rows", "sdh_engine_query_outputs"]
 SDH_COMM_ID_BYTES = 128
 
 _lib = None
@@ -169,6 +178,11 @@ def load_library(path: str = LIB_PATH):
     lib.sdh_engine_set_comm.argtypes = [P, P]
     lib.sdh_engine_push_bcast.argtypes = [P, ctypes.c_int32, ctypes.POINTER(SdhBatch), ctypes.c_int32]
     lib.sdh_engine_gather.argtypes = [P, ctypes.c_int32, ctypes.POINTER(SdhMatches)]
+    if hasattr(lib, "sdh_engine_poll_rows"):  # (SIDDHI_HIP_LIB may name an older build for an A/B run)
+        lib.sdh_engine_retain_events.argtypes = [P, ctypes.c_int64]
+        lib.sdh_engine_poll_rows.argtypes = [P, ctypes.c_int32, ctypes.POINTER(SdhRows)]
+        lib.sdh_engine_query_outputs.argtypes = [P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
     _lib = lib
     return lib
 
@@ -361,6 +375,36 @@ class HipEngine:
         tb = np.ctypeslib.as_array(m.tb, shape=(n,)).copy() if (m.tb and n) else (np.zeros(0, np.int64) if m.tb else None)
         chain = np.ctypeslib.as_array(m.chain, shape=(m.n_chain,)).copy() if m.n_chain else np.zeros(0, np.int32)
         return m.seq_base, rows, key, tb, chain
+
+    def retain_events(self, n: int):
+        """Keep the last n pushed events in HBM (sdh_engine_retain_events): what poll_rows reads."""
+        self._check(self.lib.sdh_engine_retain_events(self.h, int(n)))
+
+    def poll_rows(self, device: bool = False):
+        """The matches poll() would return, projected through their queries' select lists on the device
+        (sdh_engine_poll_rows): host arrays (query, ts, seq, cells[width, n], nulls), or the SdhRows
+        struct of HBM pointers when device is set. Cells are raw 64-bit attribute words
+        (siddhi_amd/events.py); selector.decode_rows turns them into Python values."""
+        r = SdhRows()
+        self._check(self.lib.sdh_engine_poll_rows(self.h, int(device), ctypes.byref(r)))
+        if device:
+            return r
+        n, w = r.n, r.width
+        if n == 0:
+            return (np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((w, 0), np.int64),
+                    np.zeros(0, np.uint64))
+        cells = np.ctypeslib.as_array(r.cells, shape=(w, n)).copy() if w else np.zeros((0, n), np.int64)
+        return (np.ctypeslib.as_array(r.query, shape=(n,)).copy(), np.ctypeslib.as_array(r.ts, shape=(n,)).copy(),
+                np.ctypeslib.as_array(r.seq, shape=(n,)).copy(), cells,
+                np.ctypeslib.as_array(r.nulls, shape=(n,)).copy())
+
+    def query_outputs(self, q: int) -> List[int]:
+        """The ir.T_* type of each output of query q's select list (sdh_engine_query_outputs)."""
+        n = ctypes.c_int32()
+        self._check(self.lib.sdh_engine_query_outputs(self.h, int(q), ctypes.byref(n), None, 0))
+        types = (ctypes.c_int32 * max(1, n.value))()
+        self._check(self.lib.sdh_engine_query_outputs(self.h, int(q), ctypes.byref(n), types, n.value))
+        return [int(types[c]) for c in range(n.value)]
 
     def poll_records(self) -> SdhRecords:
         """The last push's device records (sdh_engine_poll_records; SDH_FLAG_DEVICE_MATCHES): the

@@ -172,6 +172,18 @@ def project(query_ir, match_slots, log: EventLog, stream_types, dictionary, stri
             for o in query_ir.outputs]
 
 
+def decode_rows(ir, polled, dictionary: StringDictionary) -> List[list]:
+    """HipEngine.poll_rows() output (query, ts, seq, cells[width, n], nulls) -> per match the Python
+    values project() returns: the rows the device selector evaluated (sdh_engine_poll_rows)."""
+    query, _ts, _seq, cells, nulls = polled
+    rows = []
+    for i in range(len(query)):
+        mask = int(nulls[i])
+        rows.append([None if (mask >> c) & 1 else decode_value(int(cells[c, i]), o.type, dictionary)
+                     for c, o in enumerate(ir.queries[int(query[i])].outputs)])
+    return rows
+
+
 def stream_rows(ir, matches, log: EventLog, dictionary, strings, stream: str) -> List[list]:
     """Rows arriving on `stream` in delivery order: each match's projected row goes to its query's
     output stream when the match is delivered (R18 order), and through every selector chain reading
