@@ -5,7 +5,7 @@
 // (PartitionRuntime.updatePartitionStreamReceivers:312-316). The JDK is not part of the reference
 // tree; this restates its published algorithm for a single-threaded map: putVal (bins of linked
 // nodes, TreeBins past 8 nodes on tables of >= 64), addCount (resize at 3/4 load), transfer (split
-// at the lastRun, earlier nodes prepended), tryPresize. Host code (engine.hip builds the per-key
+// at the lastRun, earlier nodes prepended), tryPresize. Host code (engine_gen.hip builds the per-key
 // ranks the K_gen records carry).
 #pragma once
 #include <cstdint>

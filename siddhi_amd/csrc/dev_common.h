@@ -103,6 +103,11 @@ struct LaneOut {
   }
 };
 
+// a launch's record sink (nfa_types.h) as the kernel's LaneOut
+__device__ __forceinline__ LaneOut lane_out(const RecordSink& s) {
+  return LaneOut{s.out, s.out_cap, s.out_next, s.write_records == 2, s.rec_off, s.rec_cap, s.rec_next};
+}
+
 // Wave-buffered match output: a work group is ONE wave; its records are assembled in an LDS buffer
 // and flushed to the global buffer with one word reservation and one record-index reservation per
 // flush (a per-record atomic on the two global counters serialises the whole chip once the match

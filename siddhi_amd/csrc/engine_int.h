@@ -3,8 +3,9 @@
 // Everything here has hidden visibility: the library exports the C ABI (include/siddhi_hip.h) only.
 //
 //   engine.hip          the C ABI, knobs, sdh_engine_create (plan selection); the device match table and
-//                       its polls; the K_gen / K_seq / K_part passes; pushes; the multi-GPU exchange;
-//                       snapshot and restore
+//                       its polls; pushes; the multi-GPU exchange; snapshot and restore
+//   engine_gen.hip      the K_gen family (K_gen / K_seq / K_part / K_slab): sets and groups, arena and
+//                       table growth, the journal, partition routing and the launches of a push
 //   engine_lower.hip    IR reader, chain lowering, K_ratchet plan selection
 //   engine_ratchet.hip  K_chain and K_ratchet / K_gate / shared-pops launches
 //   engine_slab.hip     K_slab arena maintenance
@@ -115,11 +116,6 @@ struct RatchetPlan {
   }
 };
 
-// K_part shape of a query (kpart_shape in engine.hip; kind < 0: none)
-struct KPart {
-  int kind = -1, sA = 1, sB = 2, cmax = 0, n_e1 = 0, n_first = 0, n_last = 0;
-};
-
 // SDH_ALLOC_TRACE=1: one stderr line per device buffer (re)allocation (p99 push/poll latency hunts)
 inline void alloc_trace(const char* what, size_t bytes) {
   const bool on = sdh::knob("SDH_ALLOC_TRACE") != nullptr;
@@ -170,6 +166,10 @@ struct DevBuf {
     if (p) HIPCHK(hipFree(p));
     p = q;
     n = cap;
+  }
+  void swap(DevBuf& o) {  // (a grown copy takes the buffer's place; the old one is freed with `o`)
+    std::swap(p, o.p);
+    std::swap(n, o.n);
   }
   ~DevBuf() {
     if (p) (void)hipFree(p);
@@ -336,6 +336,7 @@ struct sdh_engine {
     int partition = -1;              // -1: the unpartitioned K_gen queries
     int group_base = 0, n_groups = 0;
     int64_t key_cap = 0;             // instance blocks = key_cap * n_groups (partitioned)
+    bool timed = false;              // a group has absent states (a timer queue): time passes for the set
     DevBuf<int32_t> a32;
     DevBuf<int64_t> a64;
     DevBuf<int32_t> s32;             // scratch arenas of event chunks 1.. (unpartitioned sets)
@@ -478,6 +479,7 @@ struct sdh_engine {
     DevBuf<uint64_t> journal, journal_idx;
     int64_t items = 0;                        // items of this pass's launch (0: not launched)
     int lds_words = 4096;                     // LDS rows (uint32 words) of the large tier
+    int max_na = 1;                           // the widest captured-word count of the set's shapes
     DevBuf<int32_t> defer, defer_n;           // items deferred to the large tier (nfa_slab.hip)
     int64_t deferred = 0;
     int64_t cleanings = 0, growths = 0;
@@ -597,6 +599,12 @@ struct sdh_engine {
 namespace sdh {
 namespace eng {
 
+// a small device value the host decides on: copied over the engine's stream, which is then drained
+inline void d2h_sync(sdh_engine* e, void* dst, const void* src, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+}
+
 // ---- functions that cross a unit boundary, by defining unit ----
 // engine_lower.hip
 IProgram read_ir(const void* blob, size_t len);
@@ -604,6 +612,14 @@ Lowered lower_query(const IProgram& P, int qi);
 int attr_width(int t);
 RatchetPlan ratchet_plan(const ChainQuery& c);
 sel::Program lower_outputs(const kg::LProgram& P);
+// engine_gen.hip
+void gen_build(sdh_engine* e, const std::vector<int>& qis);
+void gen_grow(sdh_engine* e, sdh_engine::GenSet& gs, int64_t keys);
+void gen_relayout(sdh_engine* e, const kg::Sizing& sz, bool remap);
+void check_fan_strings(const sdh_engine* e, int stream);
+double gen_journal_bound(sdh_engine* e, int64_t n);
+void part_grow(sdh_engine* e, sdh_engine::PartSet& ps, int64_t keys);
+void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out, double* bytes_out);
 // engine_ratchet.hip
 void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
             const std::vector<int>& qs, bool allow_chunks, bool* unordered);

@@ -37,8 +37,7 @@ void chain_grow(sdh_engine* e, int64_t want) {
   }
   HIPCHK(hipStreamSynchronize(e->stream));
   for (int b = 0; b < 2; ++b) {
-    std::swap(e->d_part[b].p, nw[b].p);
-    std::swap(e->d_part[b].n, nw[b].n);
+    e->d_part[b].swap(nw[b]);
   }
   e->pcap = (int)cap;
   e->K = cap <= 64 ? 1 : cap <= 128 ? 2 : cap <= 256 ? 4 : 8;
@@ -296,8 +295,7 @@ void ratchet_grow_rsmax(sdh_engine* e, int64_t want) {
       nw.ensure(ng * cap * WAVE);
       HIPCHK(hipMemcpy2DAsync(nw.p, nb, buf->p, ob, ob, ng, hipMemcpyDeviceToDevice, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
-      std::swap(buf->p, nw.p);
-      std::swap(buf->n, nw.n);
+      buf->swap(nw);
     }
   e->rsmax = cap;
 }

@@ -72,8 +72,7 @@ void slab_grow_keys(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t keys) {
   HIPCHK(hipMemsetAsync(nd.p + old_n, 0, (new_n - old_n) * 8, e->stream));
   if (old_n) HIPCHK(hipMemcpyAsync(nd.p, ss.dir.p, old_n * 8, hipMemcpyDeviceToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  std::swap(ss.dir.p, nd.p);
-  std::swap(ss.dir.n, nd.n);
+  ss.dir.swap(nd);
   ss.key_cap = cap;
 }
 

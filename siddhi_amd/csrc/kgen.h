@@ -422,7 +422,7 @@ KG_FN Val eval_code(const GQuery* q, const GQuery* ql, int b, int e, Attr attr, 
 }
 
 // A lane's per-query values, read from the group's lane-interleaved constant table
-// [group][slot][64] (engine.hip lane_consts): slot 0 the query id, 1 `within`, 2 + k the k-th CONST
+// [group][slot][64] (engine_gen.hip gen_build): slot 0 the query id, 1 `within`, 2 + k the k-th CONST
 // instruction of the shape in program order. A wave's 64 lanes read one slot as one coalesced 512-B
 // row instead of 64 scattered lines of 64 different GQuery structs (K_slab and K_part read them per
 // work item). col == nullptr: the lane's own query (host builds).

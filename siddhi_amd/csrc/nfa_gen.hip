@@ -41,17 +41,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   if (L.sweep) {  // every known key's clone walks the whole batch (timers), processing its own events
     kid = (uint32_t)seg;
     if ((int64_t)kid >= L.n_keys) return;
-  } else if (L.seg_begin) {
-    kid = L.seg_kid[seg];
+  } else if (L.keys.seg_begin) {
+    kid = L.keys.seg_kid[seg];
     if (kid == 0xFFFFFFFFu) return;  // events with a null partition key
-    e0 = L.seg_begin[seg];
-    e1 = e0 + L.seg_len[seg];
+    e0 = L.keys.seg_begin[seg];
+    e1 = e0 + L.keys.seg_len[seg];
   }
-  const int qi = L.lane_q[(int64_t)(L.group_base + g) * 64 + lane];
+  const int qi = L.tab.lane_q[(int64_t)(L.group_base + g) * 64 + lane];
   if (qi < 0) return;
   // wave-uniform shape template (scalar loads) + the lane's own query (constants)
-  const kg::GQuery* __restrict__ q = L.queries + L.group_tmpl[L.group_base + g];
-  const kg::GQuery* __restrict__ ql = L.queries + qi;
+  const kg::GQuery* __restrict__ q = L.tab.queries + L.tab.group_tmpl[L.group_base + g];
+  const kg::GQuery* __restrict__ ql = L.tab.queries + qi;
   // a query that does not read the stream still sees time pass if it has absent states
   const bool reads = q->recv_n[L.b.stream] != 0;
   if (!reads && q->lay.TQ == 0) return;
@@ -94,16 +94,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   c.npin = 0;
   c.n_ret = 0;
   c.stream = L.b.stream;
-  const int64_t key = L.key_of_id ? L.key_of_id[kid] : -1;
+  const int64_t key = L.keys.key_of_id ? L.keys.key_of_id[kid] : -1;
   // PartitionRuntime.cloneIfNotExist / QueryRuntime.init: seed (a sweep seeds a clone at its key's
   // first event); only top-level runtimes are start()ed (SiddhiAppRuntime.start)
   auto seed = [&]() {
     c.init_instance();
-    if (!L.key_of_id) c.start_instance(L.start_ts);
+    if (!L.keys.key_of_id) c.start_instance(L.start_ts);
     c.i32(q->lay.o_init) = 1;
   };
   if (!L.sweep && c.i32(q->lay.o_init) == 0) seed();
-  LaneOut o{L.out, L.out_cap, L.out_next, L.write_records == 2, L.rec_off, L.rec_cap, L.rec_next};
+  LaneOut o = dev::lane_out(L.sink);
   const int S = q->n_states;
   const int ncap = q->n_cap[c.stream];
   unsigned long long nrec = 0;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
       for (int n = cx.slot(se, i); n >= 0; n = cx.nd_next(n)) ++words;
     }
     ++nrec;
-    if (!L.write_records) return;
+    if (!L.sink.write_records) return;
     int64_t* r = o.reserve(words);
     if (!r) return;
     r[0] = words;
@@ -154,14 +154,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   const bool indexed = L.sweep && L.pm;
   const bool timers = !L.no_timers;  // (a chunk push fired its timers before its first event)
   const int32_t sg = indexed && L.kseg ? L.kseg[kid] : -1;
-  const int64_t sb = sg >= 0 ? L.seg_begin[sg] : 0, sl = sg >= 0 ? L.seg_len[sg] : 0;
+  const int64_t sb = sg >= 0 ? L.keys.seg_begin[sg] : 0, sl = sg >= 0 ? L.keys.seg_len[sg] : 0;
   int64_t j = 0, pos = 0;  // indexed: next own event, first batch event whose timers may still fire
   for (int64_t k = w0; c.err == kg::GE_OK;) {
     int64_t e;
     bool own;
     const bool inited = !L.sweep || c.i32(q->lay.o_init) != 0;
     if (indexed) {
-      const int64_t eo = j < sl ? L.ev_idx[sb + j] : L.b.n - 1;
+      const int64_t eo = j < sl ? L.keys.ev_idx[sb + j] : L.b.n - 1;
       if (eo < 0) break;  // (an empty batch)
       const int64_t d = inited && timers ? c.next_due() : 0x7fffffffffffffffLL;
       if (d <= L.b.ts[eo] && pos <= eo) {  // a timer stop at or before the next own event
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     } else {
       if (k >= e1) break;
       live = k >= e0;
-      e = L.ev_idx ? L.ev_idx[k] : k;
+      e = L.keys.ev_idx ? L.keys.ev_idx[k] : k;
       ++k;
       // a sweep passes time at other keys' events; a fan-out stream's events are every key's
       own = !L.sweep || L.fan_pos || (L.ev_kid && L.ev_kid[e] == kid);
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   }
   o.close();
   c.store_hot();
-  if (nrec) atomicAdd(L.rec_count, nrec);
+  if (nrec) atomicAdd(L.sink.rec_count, nrec);
   if (c.err == kg::GE_CAPACITY) atomicOr(&L.err[0], c.capk);  // which limits (kg::CAP_*)
   if (c.err == kg::GE_REFERENCE) atomicOr(&L.err[1], 1);
   if (o.over) atomicOr(&L.err[2], 1);

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   if (gi >= L.n_items) return;
   const int item = L.item_list ? L.item_list[gi] : gi;
   const int seg = item / L.n_glist, g = L.glist[item % L.n_glist];
-  const uint32_t kid = L.seg_kid[seg];
+  const uint32_t kid = L.keys.seg_kid[seg];
   if (kid == 0xFFFFFFFFu) return;  // null / foreign partition keys
   const Shape& sh = L.shapes[L.group_shape[g]];  // wave-uniform
   const int stream = L.b.stream;
@@ -87,14 +87,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   const int n_old = (int)((d0 >> 40) & 0xffff);
   const uint32_t lists = (uint32_t)(d0 >> 56);
   if (st > 0 && !((lists >> st) & 1u)) return;  // no partial waits in this state's list
-  const int qi = L.lane_q[(int64_t)(L.group_base + g) * 64 + lane];
+  const int qi = L.tab.lane_q[(int64_t)(L.group_base + g) * 64 + lane];
   const bool live = qi >= 0;
-  const kg::GQuery* __restrict__ q = L.queries + L.group_tmpl[L.group_base + g];
+  const kg::GQuery* __restrict__ q = L.tab.queries + L.tab.group_tmpl[L.group_base + g];
   // the lane's query id, `within` and filter constants: one coalesced row per value of the group's
   // lane-constant table (a lane reading its own GQuery instead touched 64 scattered lines per value)
-  const kg::LaneConsts lk{nullptr, L.lconst + ((int64_t)(L.group_base + g) * L.lc_slots) * 64 + lane};
+  const kg::LaneConsts lk{nullptr, L.tab.lconst + ((int64_t)(L.group_base + g) * L.tab.lc_slots) * 64 + lane};
   const int EW = sh.EW;
-  const int64_t e0 = L.seg_begin[seg], e1 = e0 + L.seg_len[seg];
+  const int64_t e0 = L.keys.seg_begin[seg], e1 = e0 + L.keys.seg_len[seg];
   const int ncap = q->n_cap[stream];
 
   extern __shared__ uint32_t slab_lds[];  // [lcap][EW] entries: the old block, then new partials
@@ -145,12 +145,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     e_l = lo;
   }
   SlabWaveOut o;
-  o.g = dev::LaneOut{L.out, L.out_cap, L.out_next, L.write_records == 2, L.rec_off, L.rec_cap, L.rec_next};
+  o.g = dev::lane_out(L.sink);
   o.sh = &out_sh;
   o.init();
   const int64_t within = lk.within();
   const int64_t qid = lk.qid();
-  const int64_t key = L.key_of_id[kid];
+  const int64_t key = L.keys.key_of_id[kid];
   unsigned long long nrec = 0;
   bool changed = false, lds_over = false;
   int n_new = 0;  // wave-uniform: new entries appended after the old block
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   for (int64_t t0 = e0; t0 < e1 && !lds_over; t0 += 64) {
     const int cnt = e1 - t0 < 64 ? (int)(e1 - t0) : 64;
     if (lane < cnt) {
-      const int64_t ev = L.ev_idx[t0 + lane];
+      const int64_t ev = L.keys.ev_idx[t0 + lane];
       t_ts[lane] = L.b.ts[ev];
       t_seq[lane] = L.b.seq_base + ev;
       uint32_t nb = 0;
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
         changed |= r != 0;
         const bool em = (r & R_EMIT) != 0;
         if (em) ++nrec;
-        if (L.write_records && __ballot(em) != 0) {  // (the collective emit only when a lane emits)
+        if (L.sink.write_records && __ballot(em) != 0) {  // (the collective emit only when a lane emits)
           const int words = em ? record_words(sh, e, st) : 0;
           const int64_t idx = (int64_t)pos_of(e, sh.elem[st]);
           o.emit_n(em ? 1 : 0, words, [&](auto rr) {
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     return;
   }
   if (lane == 0 && n_old) atomicAdd(&L.traffic[item & 255], (unsigned long long)n_old * EW * 4);
-  if (nrec) atomicAdd(L.rec_count, nrec);
+  if (nrec) atomicAdd(L.sink.rec_count, nrec);
   if (o.over) atomicOr(&L.err[2], 1);
   if (!__ballot(changed)) return;
   // write-back: the lane's surviving entries (old ones still in a list, markers) then its new ones

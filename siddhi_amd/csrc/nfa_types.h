@@ -287,25 +287,52 @@ constexpr int SH_BOUNDS = 4 * 64;
 constexpr uint32_t SHB_HI = 1, SHB_AGE = 2;
 
 // ------------------------------------------------------------------------------------------
-// K_gen launch (nfa_gen.hip): item = (segment of one key's events, group of 64 queries)
+// Launch-argument groups the K_gen / K_seq / K_part / K_slab launch structs embed by value
 // ------------------------------------------------------------------------------------------
 namespace kg {
 struct GQuery;
 }
 
-// the longest K_gen match record (7 + S + pool nodes words); the flat record buffer is at least twice it
-constexpr int64_t GEN_RING_MARGIN = 8192;
-
-struct GenLaunch {
+// the group tables: the queries, and per group of 64 lanes its members and its shape
+struct GroupTables {
   const kg::GQuery* queries;
   const int32_t* lane_q;      // [group][64] query index (-1 = idle lane)
   const int32_t* group_tmpl;  // [group] query whose structure every lane of the group shares
-  StreamBatch b;
+  const int64_t* lconst;      // [group][lc_slots][64] the lanes' query ids, withins, constants (kg::LaneConsts;
+  int32_t lc_slots;           //   K_part and K_slab read them, K_gen and K_seq do not)
+};
+
+// partition routing: the batch's events grouped by key, one segment per key present
+struct KeySegments {
   const int32_t* seg_begin;   // [n_seg] ranges into ev_idx (nullptr: one segment = whole batch)
   const int32_t* seg_len;
   const uint32_t* seg_kid;    // dense key id per segment (0xFFFFFFFF: dropped events)
   const int64_t* key_of_id;   // raw key per dense id (nullptr: unpartitioned, key -1)
   const int32_t* ev_idx;      // event indices grouped by key (nullptr: identity)
+};
+
+// the match-record sink (dev::lane_out builds the kernels' dev::LaneOut from it)
+struct RecordSink {
+  int64_t* out;               // flat record words: [len, qid, key, ts, seq, idx, S, (count, seqs...)xS]...
+  int64_t out_cap;            // words
+  unsigned long long* out_next;  // words used (atomic; may run past out_cap on overflow)
+  unsigned long long* rec_count;  // matches emitted (records), counted even when not written
+  int64_t* rec_off;           // write_records == 1: word offset of each record, in reservation order
+  int64_t rec_cap;
+  unsigned long long* rec_next;
+  int32_t write_records;      // 1: write; 2: write into a ring nobody reads (SDH_FLAG_DEVICE_MATCHES); 0: count only
+};
+
+// ------------------------------------------------------------------------------------------
+// K_gen launch (nfa_gen.hip): item = (segment of one key's events, group of 64 queries)
+// ------------------------------------------------------------------------------------------
+// the longest K_gen match record (7 + S + pool nodes words); the flat record buffer is at least twice it
+constexpr int64_t GEN_RING_MARGIN = 8192;
+
+struct GenLaunch {
+  GroupTables tab;
+  StreamBatch b;
+  KeySegments keys;
   int32_t groups;             // groups per segment
   int32_t group_base;         // first row of lane_q for this launch
   int64_t block_base;         // arena block of (kid, g) = block_base + kid * groups + g
@@ -313,16 +340,9 @@ struct GenLaunch {
   int64_t* a64;
   int32_t B32, B64;           // arena words per lane and block
   int32_t hot_s, hot_nu;      // LDS hot-word cache extents: max states, max node-mask words
-  int64_t* out;               // flat record words: [len, qid, key, ts, seq, idx, S, (count, seqs...)xS]...
-  int64_t out_cap;            // words
-  unsigned long long* out_next;  // words used (atomic; may run past out_cap on overflow)
+  RecordSink sink;
   int32_t n_items;
   int32_t* err;               // [0] instance capacity, [1] reference would throw, [2] output overflow
-  unsigned long long* rec_count;  // matches emitted (records), counted even when not written
-  int64_t* rec_off;           // write_records == 1: word offset of each record, in reservation order
-  int64_t rec_cap;
-  unsigned long long* rec_next;
-  int32_t write_records;      // 1: write; 2: write into a ring nobody reads (SDH_FLAG_DEVICE_MATCHES); 0: count only
   // event chunks of an unpartitioned set (kg::seq_lookback): item = chunk * groups + g; chunk 0
   // continues the persistent arena, chunk c > 0 starts a fresh instance in scratch block
   // (c-1) * groups + g and replays the template's look-back events before emitting
@@ -400,15 +420,9 @@ __host__ __device__ inline int64_t nrec_pack(int64_t lo, int64_t hi) {
 }
 
 struct PartLaunch {
-  const kg::GQuery* queries;
-  const int32_t* lane_q;      // [group][64]
-  const int32_t* group_tmpl;  // [group]
+  GroupTables tab;
   StreamBatch b;
-  const int32_t* seg_begin;   // partition routing (as GenLaunch)
-  const int32_t* seg_len;
-  const uint32_t* seg_kid;
-  const int64_t* key_of_id;
-  const int32_t* ev_idx;
+  KeySegments keys;
   int32_t groups;             // groups of this set; state block (kid, g) = kid * groups + g
   int32_t group_base;         // first row of lane_q / group_tmpl of the set
   int32_t kind;               // PartKind
@@ -423,22 +437,12 @@ struct PartLaunch {
   int64_t blocks;             // blocks per buffer
   const int32_t* cur;         // [kid] buffer holding the key's tables before this push
   int32_t* nxt;               // [kid] after it (the host swaps cur / nxt once the push succeeded)
-  int64_t* out;               // K_gen-format match records (nfa_gen.hip), as GenLaunch
-  int64_t out_cap;
-  unsigned long long* out_next;
-  unsigned long long* rec_count;
-  int64_t* rec_off;
-  int64_t rec_cap;
-  unsigned long long* rec_next;
-  int32_t write_records;
+  RecordSink sink;            // K_gen-format match records (nfa_gen.hip) beside the narrow ones
   int32_t xcd;                // items in per-XCD ranges (dev::grid_item; the grid is padded to a multiple of 8)
   int32_t sorted;             // b holds the batch in key order (position t = ev_idx's t); ev_idx still
                               // gives each position's batch index (its seq)
   int32_t* err;               // [0] entry capacity, [2] output overflow
   unsigned long long* prof;   // SDH_PART_PROF builds: per-phase clock sums (part_body.h), else null
-  const int64_t* lconst;      // [group][lc_slots][64] the lanes' query ids, withins, constants (kg::LaneConsts)
-  int32_t lc_slots;
-  int32_t pad_lc;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -452,17 +456,11 @@ struct Shape;
 }
 
 struct SlabLaunch {
-  const kg::GQuery* queries;
-  const int32_t* lane_q;      // [group][64]
-  const int32_t* group_tmpl;  // [group]
+  GroupTables tab;
   const slab::Shape* shapes;  // per shape
   const int32_t* group_shape; // [set group] -> shape
   StreamBatch b;
-  const int32_t* seg_begin;   // partition routing (as GenLaunch)
-  const int32_t* seg_len;
-  const uint32_t* seg_kid;
-  const int64_t* key_of_id;
-  const int32_t* ev_idx;
+  KeySegments keys;
   const int32_t* glist;       // set groups that read the pushed stream; item = seg * n_glist + j
   int32_t n_glist;
   int32_t n_items;
@@ -480,18 +478,9 @@ struct SlabLaunch {
   int32_t max_na;             // the widest captured-word count of the set's shapes (event staging)
   long long* live;            // [256] live-partial counters (sum = live partials)
   unsigned long long* traffic;  // [256] block bytes read + written (the launch's state traffic)
-  int64_t* out;               // K_gen-format match records, as GenLaunch
-  int64_t out_cap;
-  unsigned long long* out_next;
-  unsigned long long* rec_count;
-  int64_t* rec_off;
-  int64_t rec_cap;
-  unsigned long long* rec_next;
-  int32_t write_records;
+  RecordSink sink;            // K_gen-format match records
   int32_t xcd;                // items in per-XCD ranges (as PartLaunch)
   int32_t* err;               // [0] LDS capacity, [1] slab space, [2] output overflow
-  const int64_t* lconst;      // [group][lc_slots][64] the lanes' query ids, withins, constants (kg::LaneConsts)
-  int32_t lc_slots;
   int32_t defer_cap;          // two-tier LDS: room in defer (0: no deferral, an oversized block sets err[0])
   int32_t* defer;             // items whose block outgrew this launch's LDS rows (re-run with more LDS)
   int32_t* defer_n;
@@ -506,9 +495,7 @@ constexpr int SEQ_TMAX = 7;                   // events a stream's tail carries 
 constexpr int SEQ_TW = 2 + 2 * MAXATTR;       // tail row: ts, seq, raw words, null flags
 
 struct SeqLaunch {
-  const kg::GQuery* queries;
-  const int32_t* lane_q;      // [group][64] query index (-1 = idle lane)
-  const int32_t* group_tmpl;  // [group] shape template
+  GroupTables tab;
   const int32_t* glist;       // [n_glist] groups (rows of lane_q) this launch runs
   int32_t n_glist;
   int32_t n_chunks;           // start chunks per group
@@ -516,14 +503,7 @@ struct SeqLaunch {
   StreamBatch b;
   const int64_t* tail;        // [SEQ_TMAX][SEQ_TW]: the stream's last events before this batch
   int32_t tail_len;
-  int32_t write_records;
-  int64_t* out;               // flat K_gen-format records (nfa_gen.hip)
-  int64_t out_cap;
-  unsigned long long* out_next;
-  unsigned long long* rec_count;
-  int64_t* rec_off;           // as GenLaunch
-  int64_t rec_cap;
-  unsigned long long* rec_next;
+  RecordSink sink;            // K_gen-format records (nfa_gen.hip) beside the narrow ones
   int32_t* err;               // [2] output overflow
   int32_t xcd;                // items in per-XCD ranges (as PartLaunch)
 };

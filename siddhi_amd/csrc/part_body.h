@@ -2,7 +2,7 @@
 // family); the kernel body, instantiated by nfa_part.hip with the interpreted filters
 // (PartInterp) and by spec.hip with a shape's filters compiled to straight-line code.
 //
-// Shapes (kpart_shape in engine.hip decides; every filter in the IR's typed bytecode):
+// Shapes (kpart_shape in engine_gen.hip decides; every filter in the IR's typed bytecode):
 //   PK_OR / PK_AND  every e1=S[f1] -> e2=S[f2] or|and e3=S[f3] [within T]     (f1, f2, f3 event-only)
 //   PK_COUNT        every e1=S[f1] -> e2=S[f2] <min:max> -> e3=S[f3] [within T]
 //                   (f1, f2 event-only; f3 may read e1, e2[0], e2[last] and the current event)
@@ -215,16 +215,16 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
   const int item = (int)dev::grid_item(L.xcd);
   if (item >= L.n_items) return;
   const int seg = item / L.gn, g = L.g0 + item % L.gn;
-  const uint32_t kid = L.seg_kid[seg];
+  const uint32_t kid = L.keys.seg_kid[seg];
   if (kid == 0xFFFFFFFFu) return;  // null / foreign partition keys
-  const int64_t e0 = L.seg_begin[seg], e1 = e0 + L.seg_len[seg];
-  const int qi = L.lane_q[(int64_t)(L.group_base + g) * 64 + lane];
-  const kg::GQuery* __restrict__ q = L.queries + L.group_tmpl[L.group_base + g];  // wave-uniform shape
-  const kg::GQuery* __restrict__ ql = L.queries + (qi >= 0 ? qi : L.group_tmpl[L.group_base + g]);
+  const int64_t e0 = L.keys.seg_begin[seg], e1 = e0 + L.keys.seg_len[seg];
+  const int qi = L.tab.lane_q[(int64_t)(L.group_base + g) * 64 + lane];
+  const kg::GQuery* __restrict__ q = L.tab.queries + L.tab.group_tmpl[L.group_base + g];  // wave-uniform shape
+  const kg::GQuery* __restrict__ ql = L.tab.queries + (qi >= 0 ? qi : L.tab.group_tmpl[L.group_base + g]);
   // the lane's query id, `within` and constants from the group's lane-constant table (one coalesced
   // row per value; kg::LaneConsts), loaded once: a per-lane global load inside the event loop would
   // wait (vmcnt is in order) for every record store issued before it
-  const int64_t* __restrict__ lcol = L.lconst + ((int64_t)(L.group_base + g) * L.lc_slots) * 64 + lane;
+  const int64_t* __restrict__ lcol = L.tab.lconst + ((int64_t)(L.group_base + g) * L.tab.lc_slots) * 64 + lane;
   typename Spec::K k;
   Spec::load(k, ql, L, lcol);
   const PartOffs of = Spec::offs(L);
@@ -233,7 +233,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
   const int64_t within = lcol[kg::LC_WITHIN * 64];
   const int64_t qid = lcol[kg::LC_QID * 64];
   const int cmin = q->st[1].min, cmax = q->st[1].max;  // PK_COUNT: this shape's <min:max>
-  const int64_t key = L.key_of_id[kid];
+  const int64_t key = L.keys.key_of_id[kid];
   const int ew = RC > 0 ? EW : L.ew;
   const int64_t bw = PK_HDR + (int64_t)L.cap * ew;
   const int64_t block = (int64_t)kid * L.groups + g;
@@ -267,7 +267,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
   __shared__ uint32_t t_nul[64];
   __shared__ typename Out::Shared out_sh;
   Out o;
-  o.g = dev::LaneOut{L.out, L.out_cap, L.out_next, L.write_records == 2, L.rec_off, L.rec_cap, L.rec_next};
+  o.g = dev::lane_out(L.sink);
   o.sh = &out_sh;
   o.init();
   unsigned long long nrec = 0;
@@ -381,7 +381,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
         if (!inL3 && len >= cmax) alive = false;  // in neither list any more
       }
       if (done >= 0) ++nrec;
-      if (L.write_records && __ballot(done >= 0)) {
+      if (L.sink.write_records && __ballot(done >= 0)) {
         // the narrow record (nfa_types.h) when e1's distance fits int32, else the K_gen record
         // [words, qid, key, ts, seq, idx, 3 | stream, (1, e1), (len, chain...), (1, seq)]
         const int64_t sq = done >= 0 ? t_seq[done] : 0;
@@ -439,7 +439,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
     const int cnt = e1 - t0 < 64 ? (int)(e1 - t0) : 64;
     if (lane < cnt) {
       // (a key-ordered copy of the batch makes the tile's reads contiguous: L.sorted)
-      const int64_t e = L.ev_idx[t0 + lane], p = L.sorted ? t0 + lane : e;
+      const int64_t e = L.keys.ev_idx[t0 + lane], p = L.sorted ? t0 + lane : e;
       t_ts[lane] = L.b.ts[p];
       t_seq[lane] = L.b.seq_base + e;
       uint32_t nb = 0;
@@ -521,7 +521,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
           // side B first (its processor runs first), then side A; either empties the list
           if (fb || fa) {
             nrec += n;
-            if (L.write_records) {
+            if (L.sink.write_records) {
               const int64_t as = fb ? -1 : seq, bs = fb ? seq : -1;  // words: 7 + 2 + 2 + 1
               if (narrow_ok(n))
                 o.emit_n(n, NREC_ORAND_WORDS, [&](auto r0) {
@@ -541,7 +541,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
           // sides passing all n complete, with one side the F partials filled on the other side.
           const int c = (fa && fb) ? n : ((fb && side == 1) || (fa && side == 2)) ? F : 0;
           nrec += c;
-          if (L.write_records) {
+          if (L.sink.write_records) {
             const bool nar = narrow_ok(c);
             const int words = nar ? NREC_ORAND_WORDS : 13;  // (wide: 7 + 2 + 2 + 2)
             o.emit_n(c, words, [&](auto r0) {
@@ -601,7 +601,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
   st[0] = n;
   st[64] = (int64_t)(uint32_t)F | ((int64_t)side << 32);
   o.close();
-  if (nrec) atomicAdd(L.rec_count, nrec);
+  if (nrec) atomicAdd(L.sink.rec_count, nrec);
   if (cap_over) atomicOr(&L.err[0], 1);
   if (o.over) atomicOr(&L.err[2], 1);
 #ifdef SDH_PART_PROF

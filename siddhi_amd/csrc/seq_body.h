@@ -55,9 +55,9 @@ __device__ __forceinline__ void seq_body(const SeqLaunch& L) {
   if (it >= (int64_t)L.n_glist * L.n_chunks) return;
   const int gi = L.glist[it % L.n_glist];
   const int chunk = (int)(it / L.n_glist);
-  const int qi = L.lane_q[(int64_t)gi * 64 + lane];
-  const kg::GQuery* __restrict__ q = L.queries + L.group_tmpl[gi];
-  const kg::GQuery* __restrict__ ql = L.queries + (qi >= 0 ? qi : L.group_tmpl[gi]);
+  const int qi = L.tab.lane_q[(int64_t)gi * 64 + lane];
+  const kg::GQuery* __restrict__ q = L.tab.queries + L.tab.group_tmpl[gi];
+  const kg::GQuery* __restrict__ ql = L.tab.queries + (qi >= 0 ? qi : L.tab.group_tmpl[gi]);
   typename Spec::K k;
   Spec::load(k, ql);
   const int S = q->n_states;
@@ -81,7 +81,7 @@ __device__ __forceinline__ void seq_body(const SeqLaunch& L) {
   using Out = dev::WaveOutT<Spec::kOutW>;
   __shared__ typename Out::Shared out_sh;
   Out o;
-  o.g = dev::LaneOut{L.out, L.out_cap, L.out_next, L.write_records == 2, L.rec_off, L.rec_cap, L.rec_next};
+  o.g = dev::lane_out(L.sink);
   o.sh = &out_sh;
   o.init();
   unsigned long long nrec = 0;
@@ -163,7 +163,7 @@ __device__ __forceinline__ void seq_body(const SeqLaunch& L) {
   };
   auto emit = [&](int s) {
     ++nrec;
-    if (!L.write_records) return;
+    if (!L.sink.write_records) return;
     if (!__ballot(!nar_ok(s))) o.emit_u(nwords, [&](auto r) { put_nrec(r, s); });
     else o.emit_u(words, [&](auto r) { put_rec(r, s); });
   };
@@ -174,7 +174,7 @@ __device__ __forceinline__ void seq_body(const SeqLaunch& L) {
   auto emit_tile = [&](uint64_t m) {
     const int nl = __popcll(m);
     nrec += nl;
-    if (!L.write_records || __ballot(nl > 0) == 0) return;
+    if (!L.sink.write_records || __ballot(nl > 0) == 0) return;
     bool ok = true;
     for (uint64_t mm = m; mm; mm &= mm - 1) ok = ok && nar_ok(__builtin_ctzll(mm));
     if (!__ballot(!ok))
@@ -234,7 +234,7 @@ __device__ __forceinline__ void seq_body(const SeqLaunch& L) {
     }
     __syncthreads();
   }
-  if (nrec) atomicAdd(L.rec_count, nrec);
+  if (nrec) atomicAdd(L.sink.rec_count, nrec);
   o.close();
   if (o.over) atomicOr(&L.err[2], 1);
 }

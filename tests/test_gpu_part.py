@@ -136,6 +136,34 @@ def test_c3_family_kpart_equals_kgen():
     assert a.engine.stats().matches > 10000
 
 
+def test_c3_family_shape_compiled_equals_interpreted():
+    """The shape-compiled K_part kernels (built at engine creation from the embedded device headers,
+    SDH_SPEC=require: every shape) equal the interpreted kernel on the C3 family push by push, in
+    normal mode row for row and in device-records mode (the compiled kernel's other output buffer
+    size) match count for match count. The compiled kernels read the launch struct through headers
+    compiled at run time, so this is where a layout disagreement between the two compiles shows."""
+    from siddhi_amd.engine import SDH_FLAG_DEVICE_MATCHES
+    from siddhi_amd.workloads import c3_app, stock_events
+    src = c3_app(96)
+    for flags in (0, SDH_FLAG_DEVICE_MATCHES):
+        a = _hip_app(src, flags=flags, debug={"SDH_SPEC": "require"})
+        b = _hip_app(src, flags=flags, debug={"SDH_SPEC": "0"})
+        assert a.engine.stats().spec_kernels > 0 and b.engine.stats().spec_kernels == 0
+        for lo in (0, 20000, 20001):
+            n = 20000 if lo != 20000 else 1
+            ts, sym, price, vol = stock_events(lo, n, 1000)
+            cols = [sym, price.view(np.uint32), vol]
+            a.engine.push_columns(0, ts, cols)
+            b.engine.push_columns(0, ts, cols)
+            assert a.engine.stats().last_part_items > 0 and b.engine.stats().last_part_items > 0
+            if flags:
+                assert a.engine.stats().matches == b.engine.stats().matches
+                continue
+            for u, v in zip(a.engine.poll(), b.engine.poll()):
+                assert np.array_equal(u, v)
+        assert a.engine.stats().matches == b.engine.stats().matches > 10000
+
+
 def test_reserve_keys_presizes_and_keeps_results():
     """sdh_engine_reserve_keys sizes the per-key state up front (no growth copy inside later pushes);
     the matches equal an engine that grows as keys appear, K_gen (FORCE_GEN) and K_part alike, and a
