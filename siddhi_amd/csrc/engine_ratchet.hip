@@ -593,6 +593,8 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
       S.cs_n = e->d_shcmn.p + ng * WAVE;
       e->d_shbounds.ensure(ng * (size_t)sdh::SH_BOUNDS);
       S.bounds = e->d_shbounds.p;
+      if (const char* v = sdh::knob("SDH_RATCHET_SCATTER"))
+        S.scatter = !strcmp(v, "pair") ? sdh::SH_SCATTER_PAIR : !strcmp(v, "lane") ? sdh::SH_SCATTER_LANE : sdh::SH_SCATTER_RULE;
       e->d_shtemp.ensure(sdh_ratchet_shared_temp(n) + 16);
       return S;
     };

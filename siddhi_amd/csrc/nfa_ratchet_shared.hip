@@ -8,6 +8,9 @@
 #ifndef SDH_RATCHET_NOSTORE
 #define SDH_RATCHET_NOSTORE 0
 #endif
+#ifndef SDH_RATCHET_NOSCATTER
+#define SDH_RATCHET_NOSCATTER 0  // (timing only: the scatter's LDS writes compiled out, the records are garbage)
+#endif
 #ifndef SDH_RATCHET_MASK_CXX
 #define SDH_RATCHET_MASK_CXX 0
 #endif
@@ -208,11 +211,16 @@ __global__ __launch_bounds__(64) void ratchet_shared_carried(RatchetLaunch L, Sh
     sim_bounds(G, lane, active, flo, fhi);
     float glo = flo, ghi = fhi;  // the group's widest bounds: a pair outside them is nobody's
     int32_t gw = w32;
+    // the smallest `within` and upper bound of the active lanes: a tile inside both skips the compares
+    int32_t wmin = active ? w32 : INT32_MAX;
+    float himin = active ? fhi : __int_as_float(0x7f800000);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
       glo = fminf(glo, __shfl_xor(glo, d, WAVE));
       ghi = fmaxf(ghi, __shfl_xor(ghi, d, WAVE));
       gw = max(gw, __shfl_xor(gw, d, WAVE));
+      wmin = min(wmin, __shfl_xor(wmin, d, WAVE));
+      himin = fminf(himin, __shfl_xor(himin, d, WAVE));
     }
     const uint32_t flags = (wballot(active && fhi != __int_as_float(0x7f800000)) ? SHB_HI : 0u) |
                            (wballot(active && w32 != INT32_MAX) ? SHB_AGE : 0u);
@@ -220,8 +228,9 @@ __global__ __launch_bounds__(64) void ratchet_shared_carried(RatchetLaunch L, Sh
     b[lane] = __float_as_uint(flo);
     b[WAVE + lane] = __float_as_uint(fhi);
     b[2 * WAVE + lane] = (uint32_t)w32;
-    b[3 * WAVE + lane] = lane == 0 ? __float_as_uint(glo) : lane == 1 ? __float_as_uint(ghi) : lane == 2 ? (uint32_t)gw
-                         : lane == 3 ? flags : 0u;
+    b[3 * WAVE + lane] = lane == SHW_GLO ? __float_as_uint(glo) : lane == SHW_GHI ? __float_as_uint(ghi)
+                         : lane == SHW_GW ? (uint32_t)gw : lane == SHW_FLAGS ? flags
+                         : lane == SHW_WMIN ? (uint32_t)wmin : lane == SHW_HIMIN ? __float_as_uint(himin) : 0u;
   }
   const int64_t t_last = L.b.ts[S.n - 1];
   int nm = 0, c = n_in - 1, aged = 0, d4 = 0;
@@ -337,10 +346,11 @@ __device__ __forceinline__ void sh_take_masks(uint32_t vlo, uint32_t vhi, uint32
 // nfa_ratchet_kernel's PM 4). First the group's carried matches at the item's events, lane = pattern,
 // by ascending e2. Then the item's pairs, 64 per tile with lane = pair: the take mask of each pair
 // over the group's patterns (sh_take_masks), the pairs' entry counts scanned into offsets, one side
-// entry per event and block from two ballots, the entries scattered through an LDS window and
-// copied to the block in whole-wave contiguous stores. A tile that does not fit the block is cut at
-// the last pair that does. The group's last item writes the next deques: the carried survivors are
-// in place, U follows.
+// entry per event and block from two ballots, the entries scattered through an LDS window (one
+// wave-wide write per pair where the pairs are dense, one walk of its mask per lane where they are
+// sparse) and copied to the block in whole-wave contiguous stores. A tile that does not fit the block
+// is cut at the last pair that does. The group's last item writes the next deques: the carried
+// survivors are in place, U follows.
 __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L, SharedLaunch S) {
   __shared__ __attribute__((aligned(16))) uint32_t win[SDH_RATCHET_WIN];
   constexpr int SH_PASS = SDH_RATCHET_WIN - 4;  // entries per pass through the window (4 slots of alignment slack)
@@ -353,10 +363,17 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
   const int64_t within = G->within[lane];
   const uint32_t vlo = bt[lane], vhi = bt[WAVE + lane], vw = bt[2 * WAVE + lane];
   const float flo = __uint_as_float(vlo), fhi = __uint_as_float(vhi);
-  const float glo = __uint_as_float(bt[3 * WAVE]), ghi = __uint_as_float(bt[3 * WAVE + 1]);
-  const int32_t gw = (int32_t)bt[3 * WAVE + 2];
-  const uint32_t gflags = bt[3 * WAVE + 3];
+  const float glo = __uint_as_float(bt[3 * WAVE + SHW_GLO]), ghi = __uint_as_float(bt[3 * WAVE + SHW_GHI]);
+  const int32_t gw = (int32_t)bt[3 * WAVE + SHW_GW];
+  const uint32_t gflags = bt[3 * WAVE + SHW_FLAGS];
+  const int32_t gwmin = (int32_t)bt[3 * WAVE + SHW_WMIN];
+  const float ghimin = __uint_as_float(bt[3 * WAVE + SHW_HIMIN]);
   const uint64_t lanes_m = below64(G->n_lanes);  // (idle patterns take nothing)
+  // the pair form's lane constants: the pattern's bits of an entry, its mask bit, and the byte offset
+  // of its slot in a pair every active pattern takes (idle lanes: beyond any pass)
+  const uint32_t lp = (uint32_t)lane << 26;
+  const uint64_t lbit = 1ull << lane;
+  const uint32_t fslot4 = lane < G->n_lanes ? (uint32_t)lane * 4u : 0x40000000u;
   const size_t gb = (size_t)W.g * L.rsmax * WAVE;
   const uint32_t sb32 = (uint32_t)L.b.seq_base;
   const uint32_t c0 = (uint32_t)W.c0, c1 = (uint32_t)W.c1;  // (rec4: batches of at most 2^26 events)
@@ -474,6 +491,7 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
     const int c = __popcll(T);
     const uint64_t has = wballot(c > 0);
     if (!has) return;  // (candidates of the widest bounds, no taker: nothing is written)
+    const uint64_t fullm = wballot(T == lanes_m);  // pairs every active pattern takes
     const int incl = wave_incl_scan(c, lane), off = incl - c;
     const uint32_t jp = (uint32_t)__shfl_up((int)j, 1, WAVE);
     const uint64_t jdiff = wballot(lane == 0 || j != jp);  // the runs' first lanes
@@ -504,27 +522,58 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
         const u32x2 se = {(uint32_t)(fill + off - off_a), j};
         __builtin_amdgcn_raw_buffer_store_b64(se, wrs, cap - (sfill + rank + 1) * 8, 0, 0);
       }
-      // the entries through the window: each lane writes its next entries while they lie inside the
-      // pass, low half of T first; then the wave copies the pass out. Entry 0 of the pass sits at slot
-      // fill & 3 of the window, so a 16-B-aligned quad of the window is one of the block: the middle
-      // goes out as 16-B stores (1 KiB per wave instruction), up to three entries at either end as
-      // 4-B stores
+      // the entries through the window, a pass at a time: the scatter writes them, then the wave copies
+      // the pass out. Entry 0 of the pass sits at slot fill & 3 of the window, so a 16-B-aligned quad of
+      // the window is one of the block: the middle goes out as 16-B stores (1 KiB per wave instruction),
+      // up to three entries at either end as 4-B stores.
+      // Two forms of the scatter, chosen per block part. Pair form (lane = pattern): a scalar loop over
+      // the pairs whose entries meet the pass, one wave-wide write at consecutive slots per pair; a pair
+      // every active pattern takes needs no rank. Lane form (lane = pair): each lane writes its next
+      // entries while they lie inside the pass, low half of T first. The lane form's trips are the
+      // largest count, the pair form's the pairs with entries (nz): with nz * nz <= E the mean count
+      // E / nz is at least nz, and the pair form never takes more trips
+      const int nz = __popcll(has & chunk);
+      const bool pairform = S.scatter == SH_SCATTER_PAIR || (S.scatter == SH_SCATTER_RULE && nz * nz <= E);
       uint32_t rlo = mine ? (uint32_t)T : 0u, rhi = mine ? (uint32_t)(T >> 32) : 0u;
-      uint32_t pos = (uint32_t)(off - off_a);
+      const int rel = off - off_a;
+      uint32_t pos = (uint32_t)rel;
       const int sh = fill & 3;
       for (int w0 = 0; w0 < E; w0 += SH_PASS) {
-        uint32_t idx = pos - (uint32_t)w0;  // (beyond the pass for a lane whose entries start later)
-        while (rlo != 0 && idx < (uint32_t)SH_PASS) {
-          win[sh + idx] = d | ((uint32_t)__builtin_ctz(rlo) << 26);
-          rlo &= rlo - 1;
-          ++idx;
+        if (SDH_RATCHET_NOSCATTER) {
+        } else if (pairform) {
+          // (a pair that straddles a pass boundary is visited in both passes)
+          const uint64_t pm = wballot(mine && c > 0 && rel + c > w0 && rel < w0 + SH_PASS);
+          // (a full pair's write is not predicated: a slot outside the pass lands, clamped, on window
+          // words the flush never reads -- below slot sh, or from sh + SH_PASS to the last word)
+          const int wb4 = (sh - w0) * 4;
+          for (uint64_t fm = pm & fullm; fm;) {
+            const int k = __builtin_ctzll(fm);
+            fm &= ~(1ull << k);
+            const uint32_t x = (uint32_t)(__builtin_amdgcn_readlane(rel, k) * 4 + wb4) + fslot4;
+            const uint32_t dk = __builtin_amdgcn_readlane(d, k);
+            *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(win) + min(x, (uint32_t)(SDH_RATCHET_WIN - 1) * 4u)) = dk | lp;
+          }
+          for (uint64_t qm = pm & ~fullm; qm; qm &= qm - 1) {
+            const int k = __builtin_ctzll(qm);
+            const uint64_t Tk = (uint64_t)readlane64((int64_t)T, k);
+            const uint32_t slot = (uint32_t)(__builtin_amdgcn_readlane(rel, k) - w0) + (uint32_t)wave_mbcnt(Tk);
+            const uint32_t dk = __builtin_amdgcn_readlane(d, k);
+            if ((Tk & lbit) != 0 && slot < (uint32_t)SH_PASS) win[sh + slot] = dk | lp;
+          }
+        } else {
+          uint32_t idx = pos - (uint32_t)w0;  // (beyond the pass for a lane whose entries start later)
+          while (rlo != 0 && idx < (uint32_t)SH_PASS) {
+            win[sh + idx] = d | ((uint32_t)__builtin_ctz(rlo) << 26);
+            rlo &= rlo - 1;
+            ++idx;
+          }
+          while (rlo == 0 && rhi != 0 && idx < (uint32_t)SH_PASS) {
+            win[sh + idx] = d | ((32u + (uint32_t)__builtin_ctz(rhi)) << 26);
+            rhi &= rhi - 1;
+            ++idx;
+          }
+          pos = (uint32_t)w0 + idx;
         }
-        while (rlo == 0 && rhi != 0 && idx < (uint32_t)SH_PASS) {
-          win[sh + idx] = d | ((32u + (uint32_t)__builtin_ctz(rhi)) << 26);
-          rhi &= rhi - 1;
-          ++idx;
-        }
-        pos = (uint32_t)w0 + idx;
         __syncthreads();
         const int n = min(SH_PASS, E - w0), g0 = fill + w0;  // (g0 - sh is a multiple of 4)
         const int nh = min(n, (4 - sh) & 3), nq = (n - nh) >> 2, nt = n - nh - 4 * nq;
@@ -562,9 +611,15 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
     const bool cand0 = live0 && k0 >= glo && k0 <= ghi && a0 <= gw, cand1 = live1 && k1 >= glo && k1 <= ghi && a1 <= gw;
     if (wballot(cand0 || cand1) == 0) continue;  // outside the group's widest bounds: nobody's
     uint64_t T0, T1;
-    if (gflags == 0) sh_take_masks<false, false>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
-    else if (gflags == SHB_AGE) sh_take_masks<false, true>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
-    else if (gflags == SHB_HI) sh_take_masks<true, false>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    // a compare every active pattern passes for every candidate of both tiles is dropped: with
+    // age <= min w32 (key <= min fhi) `a <= w` (`k <= hi`) holds for each of them, equality included;
+    // the other pairs' masks are zeroed below
+    uint32_t fl = gflags;
+    if ((fl & SHB_AGE) && wballot((cand0 && a0 > gwmin) || (cand1 && a1 > gwmin)) == 0) fl &= ~SHB_AGE;
+    if ((fl & SHB_HI) && wballot((cand0 && !(k0 <= ghimin)) || (cand1 && !(k1 <= ghimin))) == 0) fl &= ~SHB_HI;
+    if (fl == 0) sh_take_masks<false, false>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    else if (fl == SHB_AGE) sh_take_masks<false, true>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
+    else if (fl == SHB_HI) sh_take_masks<true, false>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
     else sh_take_masks<true, true>(vlo, vhi, vw, k0, a0, k1, a1, T0, T1);
     T0 = cand0 ? T0 & lanes_m : 0;
     T1 = cand1 ? T1 & lanes_m : 0;

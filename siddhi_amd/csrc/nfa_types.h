@@ -280,11 +280,18 @@ struct SharedLaunch {
   // the groups' lane constants, [g][SH_BOUNDS] words written by ratchet_shared_carried for the emission
   // kernel's wave-uniform reads: rows of 64 {flo bits}, {fhi bits}, {w32} (sim_bounds; the 32-bit
   // `within`, -1 for idle lanes), then {glo bits, ghi bits, gw, flags}: the group's widest bounds and
-  // SHB_HI (an active lane's fhi is finite) | SHB_AGE (an active lane has a `within`)
+  // SHB_HI (an active lane's fhi is finite) | SHB_AGE (an active lane has a `within`), then {the smallest
+  // w32, the smallest fhi bits} over the active lanes: a tile whose candidates are all within both needs
+  // neither compare (words SHW_* of the fourth row)
   uint32_t* bounds;
+  // how a tile's entries reach the LDS window (SDH_RATCHET_SCATTER): SH_SCATTER_RULE chooses per block
+  // part (lane = pattern, one pair per trip, iff pairs-with-entries^2 <= entries), or one form forced
+  int32_t scatter;
 };
 constexpr int SH_BOUNDS = 4 * 64;
 constexpr uint32_t SHB_HI = 1, SHB_AGE = 2;
+constexpr int SHW_GLO = 0, SHW_GHI = 1, SHW_GW = 2, SHW_FLAGS = 3, SHW_WMIN = 4, SHW_HIMIN = 5;
+constexpr int32_t SH_SCATTER_RULE = 0, SH_SCATTER_PAIR = 1, SH_SCATTER_LANE = 2;
 
 // ------------------------------------------------------------------------------------------
 // Launch-argument groups the K_gen / K_seq / K_part / K_slab launch structs embed by value
