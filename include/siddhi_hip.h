@@ -476,6 +476,16 @@ int sdh_engine_debug_shared_pushes(sdh_engine* e, int64_t* out);
  * streaming read over `bytes`-sized buffers on `device`, in GB/s -- the measured ceiling the bench
  * reports its roofline fraction against beside the 8 TB/s peak. */
 int sdh_calibrate_hbm(int32_t device, int64_t bytes, int32_t iters, double* copy_gbps, double* read_gbps);
+/* Diagnostic: best-of-`iters` write-only rate over a `bytes`-sized buffer of its own on `device`, in
+ * GB/s of bytes stored. mode 0: a linear fill, 16 B per lane, params = {nt}. mode 1: the K_ratchet
+ * emission kernel's store stream alone (one wave per workgroup claims blocks from a counter and fills
+ * them in bursts of 1-KiB stores), params = {side, claim, nt, block KiB (16 / 64 / 256), burst KiB
+ * (4 / 8 / 16), ragged}: `side` 8-byte side entries per block walking down from its end (negative:
+ * that many written whole at block close), `claim` 1 claims one block ahead, `nt` 1 sets the
+ * non-temporal bit, `ragged` 1 starts and ends every burst with three dword stores. SDH_E_INVALID on
+ * any other value. */
+int sdh_calibrate_store(int32_t device, int64_t bytes, int32_t iters, int32_t mode, const int32_t* params,
+                        double* out_gbps);
 /* Library version / build info string (static storage). */
 const char* sdh_version(void);
 /* "src <hash> gfx950": the hash of the engine sources the library was built from

@@ -14,6 +14,9 @@
 #ifndef SDH_RATCHET_MASK_CXX
 #define SDH_RATCHET_MASK_CXX 0
 #endif
+#ifndef SDH_RATCHET_NT
+#define SDH_RATCHET_NT 1  // the flush's 16-B stores carry the non-temporal policy bit (0: the default policy, to measure against)
+#endif
 
 namespace sdh {
 
@@ -586,7 +589,7 @@ __global__ __launch_bounds__(64) void nfa_ratchet_shared_kernel(RatchetLaunch L,
           const int q = q0 + lane;
           if (q < nq) {
             const u32x4 v = reinterpret_cast<const u32x4*>(win)[((sh + nh) >> 2) + q];  // (sh + nh is 0 or 4)
-            if (!SDH_RATCHET_NOSTORE) __builtin_amdgcn_raw_buffer_store_b128(v, wrs, (g0 + nh + 4 * q) * 4, 0, 0);
+            if (!SDH_RATCHET_NOSTORE) __builtin_amdgcn_raw_buffer_store_b128(v, wrs, (g0 + nh + 4 * q) * 4, 0, SDH_RATCHET_NT ? 2 : 0);
           }
         }
         __syncthreads();

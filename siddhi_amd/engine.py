@@ -116,7 +116,7 @@ EXPORTS = ["sdh_engine_create", "sdh_engine_push", "sdh_engine_flush", "sdh_engi
            "sdh_engine_pending_matches", "sdh_engine_start", "sdh_engine_advance_time", "sdh_engine_stats",
            "sdh_engine_snapshot", "sdh_engine_state_bytes",
            "sdh_engine_restore", "sdh_free", "sdh_engine_destroy", "sdh_last_error", "sdh_version",
-           "sdh_engine_debug_digest", "sdh_engine_set_strings", "sdh_calibrate_hbm", "sdh_build_info",
+           "sdh_engine_debug_digest", "sdh_engine_set_strings", "sdh_calibrate_hbm", "sdh_calibrate_store", "sdh_build_info",
            "sdh_engine_push_stats", "sdh_comm_get_id", "sdh_comm_create", "sdh_comm_create_local",
            "sdh_comm_destroy", "sdh_comm_last_error", "sdh_engine_set_comm", "sdh_engine_push_bcast",
            "sdh_engine_gather", "sdh_engine_reserve", "sdh_engine_reserve_keys", "sdh_engine_poll_records",
@@ -169,6 +169,9 @@ def load_library(path: str = LIB_PATH):
     lib.sdh_engine_set_strings.argtypes = [P, ctypes.c_int64, P, P, P]
     D = ctypes.POINTER(ctypes.c_double)
     lib.sdh_calibrate_hbm.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, D, D]
+    if hasattr(lib, "sdh_calibrate_store"):  # (as below: an older build named by SIDDHI_HIP_LIB lacks it)
+        lib.sdh_calibrate_store.argtypes = [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.POINTER(ctypes.c_int32), D]
     lib.sdh_comm_get_id.argtypes = [P, ctypes.c_size_t]
     lib.sdh_comm_create.argtypes = [P, ctypes.c_size_t, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(P)]
@@ -581,3 +584,28 @@ def calibrate_hbm(device: int = 0, nbytes: int = 4 << 30, iters: int = 5):
     if rc != SDH_OK:
         raise EngineError(rc, "sdh_calibrate_hbm failed")
     return c.value, r.value
+
+
+STORE_SIDE_WHOLE = -170  # calibrate_store's `side`: the headline's 170 entries per block, written whole at block close
+
+
+def calibrate_store(device: int = 0, nbytes: int = 16 << 30, iters: int = 5, mode: str = "linear", *, side: int = 0,
+                    claim: int = 0, nt: int = 0, block_kib: int = 64, burst_kib: int = 8, ragged: int = 0) -> float:
+    """Write-only GB/s (sdh_calibrate_store). mode "linear": 16 B per lane, grid-stride. mode "block": K_ratchet's
+    emission store stream alone: `side` 8-byte side entries per block (negative: that many written whole at block
+    close), `claim` 1 claims one block ahead, `nt` sets the non-temporal bit, `ragged` 1 ends every burst in dwords."""
+    if mode not in ("linear", "block"):
+        raise ValueError(f"mode {mode!r}: linear or block")
+    if (nt not in (0, 1) or claim not in (0, 1) or ragged not in (0, 1) or block_kib not in (16, 64, 256)
+            or burst_kib not in (4, 8, 16) or not -1024 <= side <= 1024 or nbytes < 1 << 20 or iters < 1):
+        raise ValueError("calibrate_store: argument out of range")
+    lib = load_library()
+    if mode == "linear":
+        params = (ctypes.c_int32 * 6)(nt, 0, 0, 0, 0, 0)
+    else:
+        params = (ctypes.c_int32 * 6)(side, claim, nt, block_kib, burst_kib, ragged)
+    out = ctypes.c_double()
+    rc = lib.sdh_calibrate_store(device, nbytes, iters, 0 if mode == "linear" else 1, params, ctypes.byref(out))
+    if rc != SDH_OK:
+        raise EngineError(rc, "sdh_calibrate_store failed")
+    return out.value
