@@ -408,6 +408,11 @@ int sdh_engine_reserve_keys(sdh_engine* e, int64_t keys);
  * and again after sdh_engine_restore; a missing id fails that push with SDH_E_INVALID. */
 int sdh_engine_set_strings(sdh_engine* e, int64_t n, const int32_t* ids, const int32_t* java_hash,
                            const int32_t* utf16_len);
+/* The engine's whole state as one blob (free it with sdh_free), and back into an engine created from the
+ * same program. A blob the restore refuses at its first checks (magic, version, another program, a fixed
+ * K_chain capacity) leaves the engine as it was. One that fails later (truncated, a mismatching
+ * section) has been loaded in part: the call returns its error as before and the engine is unusable,
+ * every later call failing with SDH_E_CAPACITY, until a restore succeeds. */
 int sdh_engine_snapshot(sdh_engine* e, void** blob, size_t* len);
 int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len);
 void sdh_free(void* p);

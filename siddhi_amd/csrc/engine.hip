@@ -1,7 +1,8 @@
 // engine.hip -- host side of libsiddhi_hip.so: plan selection, HBM state management, batching
 // and match hand-off. Implements include/siddhi_hip.h.
 // IR lowering is in engine_lower.hip, the K_gen / K_seq / K_part / K_slab passes in engine_gen.hip, the
-// K_chain and K_ratchet launches in engine_ratchet.hip, the K_slab arena in engine_slab.hip (engine_int.h).
+// K_chain and K_ratchet launches in engine_ratchet.hip, the K_slab arena in engine_slab.hip, the snapshot
+// blob in engine_snap.hip (engine_int.h).
 //
 // The reference has no device boundary; the engine is the GpuStateStreamRuntime half that replaces
 // StateInputStreamParser's object graph (core/util/parser/StateInputStreamParser.java:77-398) with
@@ -1220,6 +1221,41 @@ thread_local std::string g_create_error;
 
 }  // namespace
 
+// ---- snapshot section (engine_snap.hip): the event store (do_retain, store_append) ----
+// cap, row words, the first retained seq, then the retained rows in seq order
+void sdh::eng::snap_save_events(sdh_engine* e, snap::Writer& w) {
+  const int64_t lo = std::max(e->ev_first, e->seq - e->ev_cap), n = e->seq - lo;
+  w.put(e->ev_cap);
+  w.put(e->ev_w);
+  w.put(lo);
+  // (the ring holds them in at most two runs: up to its end, then from its start)
+  const int64_t r0 = lo & (e->ev_cap - 1), n0 = std::min(n, e->ev_cap - r0);
+  put_dev(w, e->ev_rows.p + r0 * e->ev_w, (size_t)n0 * e->ev_w * 8);
+  put_dev(w, e->ev_rows.p, (size_t)(n - n0) * e->ev_w * 8);
+}
+
+// a retaining engine takes the snapshot's retained rows (those that fit its ring); a snapshot without
+// them (`stored` false: version 8), or an engine that keeps no events, leaves the store empty
+void sdh::eng::snap_load_events(sdh_engine* e, snap::Reader& r, bool stored) {
+  e->ev_first = e->seq;
+  if (!stored) return;
+  const int64_t scap = r.get(), sw = r.get(), lo = r.get();
+  const int64_t n = e->seq - lo;
+  snap::need(scap >= 1 && sw >= 2 && sw <= 2 + MAXATTR && lo >= 0 && n >= 0 && n <= scap &&
+                 (size_t)n * (size_t)sw <= r.left(), "bad snapshot event store");
+  if (!e->ev_cap) {
+    r.skip((size_t)(n * sw));
+    return;
+  }
+  snap::need(sw == e->ev_w, "snapshot of a different program");
+  const int64_t keep = std::min(n, e->ev_cap), first = e->seq - keep;
+  r.skip((size_t)((n - keep) * sw));
+  const int64_t r0 = first & (e->ev_cap - 1), n0 = std::min(keep, e->ev_cap - r0);
+  get_dev(r, e->ev_rows.p + r0 * e->ev_w, (size_t)n0 * sw * 8);
+  get_dev(r, e->ev_rows.p, (size_t)(keep - n0) * sw * 8);
+  e->ev_first = first;
+}
+
 extern "C" {
 
 const char* sdh_version(void) { return "libsiddhi_hip 0.2 (gfx950: K_ratchet, K_chain, K_gen, K_seq; device R18 poll)"; }
@@ -1766,28 +1802,15 @@ int sdh_engine_stats(sdh_engine* e, sdh_stats* out) {
   });
 }
 
-// snapshot: [magic][version][n_q][pcap][gB32][gB64][R][N][LC][started][start_ts][seq][n_streams][prev_ts...]
-// then per query
-// header + table, ratchet deques, K_gen arenas + key tables, K_seq tails
-constexpr int64_t SNAP_MAGIC = 0x5344485350415254LL;
-constexpr int64_t SNAP_VERSION = 8;
-constexpr int64_t SNAP_VERSION_EVENTS = 9;  // version 8 followed by the event store (sdh_engine_retain_events)
 // Device memory of the sparse K_slab state: the live blocks' bytes, the slab's reserved bytes (live
 // blocks, not yet reclaimed superseded ones, and free room) and the directory's
 int sdh_engine_state_bytes(sdh_engine* e, int64_t* live_bytes, int64_t* reserved_bytes, int64_t* dir_bytes) {
   if (!e) return SDH_E_INVALID;
   return guard(e, [&]() {
     int64_t lb = 0, rb = 0, db = 0;
-    DevBuf<unsigned long long> acc;
-    acc.ensure(1);
     for (auto& up : e->ssets) {
       auto& ss = *up;
-      HIPCHK(hipMemsetAsync(acc.p, 0, 8, e->stream));
-      HIPCHK(sdh_slab_live_words(ss.dir.p, ss.key_cap * ss.n_groups, ss.n_groups, ss.d_group_ew.p, acc.p, e->stream));
-      unsigned long long w = 0;
-      HIPCHK(hipMemcpyAsync(&w, acc.p, 8, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      lb += (int64_t)w * 4;
+      lb += slab_live_words(e, ss) * 4;
       for (int64_t c : ss.cap) rb += c * 4;
       db += ss.key_cap * ss.n_groups * 8;
     }
@@ -1814,151 +1837,11 @@ int sdh_engine_snapshot(sdh_engine* e, void** blob, size_t* len) {
   if (!e || !blob || !len) return SDH_E_INVALID;
   return guard(e, [&]() {
     HIPCHK(hipStreamSynchronize(e->stream));
-    const size_t nq = e->lq.size();
-    const size_t tbl = (size_t)NF * e->pcap;
-    // (an engine that keeps events writes version 9: version 8 and, at the end, the event store)
-    std::vector<int64_t> w{SNAP_MAGIC, e->ev_cap ? SNAP_VERSION_EVENTS : SNAP_VERSION, (int64_t)nq, e->pcap, e->gB32, e->gB64,
-                           e->gsz.R, e->gsz.N, e->gsz.LC, e->started ? 1 : 0, e->start_ts, e->seq,
-                           (int64_t)e->prev_ts.size()};
-    w.insert(w.end(), e->prev_ts.begin(), e->prev_ts.end());
-    for (size_t q = 0; q < nq; ++q) {
-      InstHeader h;
-      HIPCHK(hipMemcpy(&h, e->d_hdr[e->cur[q]].p + q, sizeof h, hipMemcpyDeviceToHost));
-      w.push_back(h.seed_alive);
-      w.push_back(h.n_live);
-      size_t o = w.size();
-      w.resize(o + tbl);
-      HIPCHK(hipMemcpy(&w[o], e->d_part[e->cur[q]].p + q * tbl, tbl * 8, hipMemcpyDeviceToHost));
-    }
-    // K_ratchet deques: per group, per lane: n then n x (ts0, seq, key)
-    const size_t ng = e->rg.size();
-    w.push_back((int64_t)ng);
-    for (size_t g = 0; g < ng; ++g) {
-      const int b = e->rcur[g];
-      RatchetState rs;
-      HIPCHK(hipMemcpy(&rs, e->d_rst[b].p + g, sizeof rs, hipMemcpyDeviceToHost));
-      std::vector<int64_t> t(e->rsmax * WAVE), sq(e->rsmax * WAVE), ky(e->rsmax * WAVE);
-      const size_t o = g * e->rsmax * WAVE;
-      HIPCHK(hipMemcpy(t.data(), e->d_rts[b].p + o, t.size() * 8, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(sq.data(), e->d_rsq[b].p + o, sq.size() * 8, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(ky.data(), e->d_rky[b].p + o, ky.size() * 8, hipMemcpyDeviceToHost));
-      for (int l = 0; l < WAVE; ++l) {
-        w.push_back(rs.n[l]);
-        for (int i = 0; i < rs.n[l]; ++i) {
-          w.push_back(t[i * WAVE + l]);
-          w.push_back(sq[i * WAVE + l]);
-          w.push_back(ky[i * WAVE + l]);
-        }
-      }
-    }
-    // K_gen sets: instance arenas (Snapshotable state of every pre-processor of every instance)
-    // and, for partitions, the key table (PartitionRuntime's key -> instance map)
-    w.push_back((int64_t)e->gsets.size());
-    auto put_dev = [&](const void* dptr, size_t bytes) {
-      const size_t o = w.size();
-      w.resize(o + (bytes + 7) / 8);
-      if (bytes) HIPCHK(hipMemcpy(&w[o], dptr, bytes, hipMemcpyDeviceToHost));
-    };
-    for (auto& up : e->gsets) {
-      auto& gs = *up;
-      const int64_t blocks = gs.partition < 0 ? gs.n_groups : gs.key_cap * gs.n_groups;
-      w.push_back(gs.partition);
-      w.push_back(gs.key_cap);
-      w.push_back(blocks);
-      put_dev(gs.a32.p, (size_t)blocks * e->gB32 * 64 * 4);
-      put_dev(gs.a64.p, (size_t)blocks * e->gB64 * 64 * 8);
-    }
-    // partition key tables (PartitionRuntime's key -> instance map)
-    w.push_back((int64_t)e->routes.size());
-    for (auto& rp : e->routes) {
-      w.push_back(rp ? 1 : 0);
-      if (!rp) continue;
-      const size_t slots = (size_t)rp->tmask + 2;
-      w.push_back((int64_t)slots);
-      put_dev(rp->tkey.p, slots * 8);
-      put_dev(rp->tid.p, slots * 4);
-      put_dev(rp->n_keys.p, 4);
-      put_dev(rp->key_of_id.p, (size_t)rp->max_keys * 8);
-      // fan-out partitions: the keys' creation order (the junction maps' insertion order)
-      w.push_back(rp->kkind);
-      w.push_back(rp->nk_seen);
-      w.push_back((int64_t)rp->korder_kid.size());
-      for (size_t j = 0; j < rp->korder_kid.size(); ++j) {
-        w.push_back(rp->korder_kid[j]);
-        w.push_back(rp->korder_key[j]);
-      }
-    }
-    // K_part tables: both buffers and the per-key selector
-    w.push_back((int64_t)e->psets.size());
-    for (auto& pp : e->psets) {
-      auto& ps = *pp;
-      w.push_back(ps.partition);
-      w.push_back(ps.kind);
-      w.push_back(ps.cap);
-      w.push_back(ps.key_cap);
-      put_dev(ps.st.p, (size_t)2 * ps.key_cap * ps.n_groups * ps.bw() * 64 * 8);
-      put_dev(ps.cur.p, (size_t)ps.key_cap * 4);
-    }
-    // K_seq: each stream's tail (the only state its windowed sequences carry between pushes)
-    w.push_back((int64_t)e->seq_tail.size());
-    for (size_t st = 0; st < e->seq_tail.size(); ++st) {
-      w.push_back(e->seq_tail_len[st]);
-      put_dev(e->seq_tail[st].p, SEQ_TMAX * SEQ_TW * 8);
-    }
-    // K_slab: the live blocks packed into one ring, the directory pointing into it, the counters
-    w.push_back((int64_t)e->ssets.size());
-    for (auto& up : e->ssets) {
-      auto& ss = *up;
-      const int64_t n_dir = ss.key_cap * ss.n_groups;
-      DevBuf<unsigned long long> acc, ph, pt;
-      acc.ensure(1);
-      ph.ensure(1);
-      pt.ensure(1);
-      HIPCHK(hipMemset(acc.p, 0, 8));
-      HIPCHK(hipMemset(ph.p, 0, 8));
-      HIPCHK(hipMemset(pt.p, 0, 8));
-      HIPCHK(sdh_slab_live_words(ss.dir.p, n_dir, ss.n_groups, ss.d_group_ew.p, acc.p, e->stream));
-      unsigned long long words = 0;
-      HIPCHK(hipMemcpyAsync(&words, acc.p, 8, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      DevBuf<uint64_t> dcopy;
-      DevBuf<uint32_t> packed;
-      dcopy.ensure(std::max<int64_t>(1, n_dir));
-      packed.ensure(std::max<size_t>(1, (size_t)words));
-      if (n_dir) HIPCHK(hipMemcpy(dcopy.p, ss.dir.p, n_dir * 8, hipMemcpyDeviceToDevice));
-      DevBuf<uint32_t*> pr;
-      DevBuf<int64_t> pc;
-      pr.ensure(1);
-      pc.ensure(1);
-      const int64_t pcap = std::max<int64_t>(4, (int64_t)words);
-      HIPCHK(hipMemcpy(pr.p, &packed.p, sizeof(uint32_t*), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(pc.p, &pcap, 8, hipMemcpyHostToDevice));
-      if (words && !slab_move_raw(e, ss, dcopy.p, ss.d_ring.p, ss.d_cap.p, ss.tail.p, ss.nsub,
-                                  std::vector<unsigned long long>(ss.nsub, ~0ull), {}, pr.p, pc.p, ph.p, pt.p, 1))
-        throw Error(SDH_E_DEVICE, "K_slab snapshot: packing failed");
-      w.push_back(ss.partition);
-      w.push_back(ss.key_cap);
-      w.push_back(ss.n_groups);
-      w.push_back(ss.lds_words);
-      w.push_back((int64_t)words);
-      put_dev(dcopy.p, (size_t)n_dir * 8);
-      put_dev(packed.p, (size_t)words * 4);
-      put_dev(ss.live.p, 256 * 8);
-    }
-    // the event store: cap, row words, the first retained seq, then the retained rows in seq order
-    if (e->ev_cap) {
-      const int64_t lo = std::max(e->ev_first, e->seq - e->ev_cap), n = e->seq - lo;
-      w.push_back(e->ev_cap);
-      w.push_back(e->ev_w);
-      w.push_back(lo);
-      // (the ring holds them in at most two runs: up to its end, then from its start)
-      const int64_t r0 = lo & (e->ev_cap - 1), n0 = std::min(n, e->ev_cap - r0);
-      put_dev(e->ev_rows.p + r0 * e->ev_w, (size_t)n0 * e->ev_w * 8);
-      put_dev(e->ev_rows.p, (size_t)(n - n0) * e->ev_w * 8);
-    }
-    *len = w.size() * 8;
+    snap::Writer w;
+    snap_save(e, w);
+    *len = w.words().size() * 8;
     *blob = malloc(*len);
-    memcpy(*blob, w.data(), *len);
+    memcpy(*blob, w.words().data(), *len);
     return SDH_OK;
   });
 }
@@ -1966,217 +1849,7 @@ int sdh_engine_snapshot(sdh_engine* e, void** blob, size_t* len) {
 int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len) {
   if (!e || !blob) return SDH_E_INVALID;
   return guard(e, [&]() {
-    const int64_t* w = (const int64_t*)blob;
-    size_t nw = len / 8, i = 0;
-    auto nx = [&]() {
-      if (i >= nw) throw Error(SDH_E_INVALID, "snapshot truncated");
-      return w[i++];
-    };
-    if (nx() != SNAP_MAGIC) throw Error(SDH_E_INVALID, "bad snapshot magic");
-    const int64_t version = nx();
-    if (version != SNAP_VERSION && version != SNAP_VERSION_EVENTS)
-      throw Error(SDH_E_INVALID, "snapshot of another format version");
-    const size_t nq = (size_t)nx();
-    const int64_t spcap = nx();  // the snapshot's K_chain table capacity
-    if (nq != e->lq.size() || spcap < 64 || spcap % 64 || spcap > (1 << 24))
-      throw Error(SDH_E_INVALID, "snapshot of a different program");
-    if (spcap != e->pcap && !e->chain_growing)
-      throw Error(SDH_E_INVALID, fmt("snapshot of K_chain tables of %lld partials per query: this engine's are fixed at "
-                                     "%d (partials_per_inst)", (long long)spcap, e->pcap));
-    const int64_t b32 = nx(), b64 = nx();
-    kg::Sizing sz;
-    sz.R = (int)nx();
-    sz.N = (int)nx();
-    sz.LC = (int)nx();
-    if (sz.R < 1 || sz.R > kg::GMAXPOOL || sz.N < 1 || sz.N > kg::GMAXPOOL || sz.LC < 1 || sz.LC > (1 << 16))
-      throw Error(SDH_E_INVALID, "bad snapshot K_gen pool sizing");
-    // the snapshot's pools may have grown past this engine's: take its sizing (arenas are loaded below)
-    if (sz.R != e->gsz.R || sz.N != e->gsz.N || sz.LC != e->gsz.LC) gen_relayout(e, sz, false);
-    if (b32 != e->gB32 || b64 != e->gB64)
-      throw Error(SDH_E_INVALID, "snapshot of a different K_gen arena layout (another build or pool sizing)");
-    e->started = nx() != 0;  // the runtime's start time (absent states' schedules)
-    e->start_ts = nx();
-    e->seq = nx();
-    const size_t ns = (size_t)nx();
-    if (ns != e->prev_ts.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    for (auto& t : e->prev_ts) t = nx();
-    // a growing engine adopts the snapshot's larger tables; smaller ones load into the lanes they have
-    if (spcap > e->pcap) chain_grow(e, spcap);
-    const size_t tbl = (size_t)NF * e->pcap, stbl = (size_t)NF * spcap;
-    std::vector<int64_t> rows(tbl);
-    for (size_t q = 0; q < nq; ++q) {
-      InstHeader h{(int32_t)nx(), (int32_t)nx(), 0, 0};
-      if (i + stbl > nw) throw Error(SDH_E_INVALID, "snapshot truncated");
-      for (int f = 0; f < NF; ++f) {
-        int64_t* row = rows.data() + (size_t)f * e->pcap;
-        std::copy(&w[i + (size_t)f * spcap], &w[i + (size_t)(f + 1) * spcap], row);
-        std::fill(row + spcap, row + e->pcap, f == F_STATE ? -1 : 0);
-      }
-      HIPCHK(hipMemcpy(e->d_hdr[e->cur[q]].p + q, &h, sizeof h, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_part[e->cur[q]].p + q * tbl, rows.data(), tbl * 8, hipMemcpyHostToDevice));
-      i += stbl;
-    }
-    const size_t ng = (size_t)nx();
-    if (ng != e->rg.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    // deques in snapshot order; the persisted capacity grows to the longest one first
-    std::vector<size_t> at(ng);
-    int64_t longest = 0;
-    for (size_t g = 0; g < ng; ++g) {
-      at[g] = i;
-      for (int l = 0; l < WAVE; ++l) {
-        const int64_t nl = nx();
-        if (nl < 0 || nl > ((int64_t)1 << 26) || i + 3 * (size_t)nl > nw)
-          throw Error(SDH_E_INVALID, "bad snapshot deque length");
-        longest = std::max(longest, nl);
-        i += 3 * (size_t)nl;
-      }
-    }
-    ratchet_grow_rsmax(e, longest);
-    const size_t i_end = i;
-    for (size_t g = 0; g < ng; ++g) {
-      i = at[g];
-      const int b = e->rcur[g];
-      RatchetState rs{};
-      std::vector<int64_t> t(e->rsmax * WAVE, 0), sq(e->rsmax * WAVE, 0), ky(e->rsmax * WAVE, 0);
-      for (int l = 0; l < WAVE; ++l) {
-        const int64_t nl = nx();
-        rs.n[l] = (int32_t)nl;
-        for (int i = 0; i < nl; ++i) {
-          t[i * WAVE + l] = nx();
-          sq[i * WAVE + l] = nx();
-          ky[i * WAVE + l] = nx();
-        }
-      }
-      const size_t o = g * e->rsmax * WAVE;
-      HIPCHK(hipMemcpy(e->d_rst[b].p + g, &rs, sizeof rs, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_rts[b].p + o, t.data(), t.size() * 8, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_rsq[b].p + o, sq.data(), sq.size() * 8, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_rky[b].p + o, ky.data(), ky.size() * 8, hipMemcpyHostToDevice));
-    }
-    i = i_end;
-    if ((size_t)nx() != e->gsets.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    auto get_dev = [&](void* dptr, size_t bytes) {
-      const size_t nw8 = (bytes + 7) / 8;
-      if (i + nw8 > nw) throw Error(SDH_E_INVALID, "snapshot truncated");
-      if (bytes) HIPCHK(hipMemcpy(dptr, &w[i], bytes, hipMemcpyHostToDevice));
-      i += nw8;
-    };
-    for (auto& up : e->gsets) {
-      auto& gs = *up;
-      if (nx() != gs.partition) throw Error(SDH_E_INVALID, "snapshot of a different program");
-      const int64_t key_cap = nx(), blocks = nx();
-      if (gs.partition >= 0) {
-        gen_grow(e, gs, key_cap);
-        if (gs.key_cap != key_cap) throw Error(SDH_E_INVALID, "snapshot key capacity mismatch");
-      }
-      const int64_t want_blocks = gs.partition < 0 ? gs.n_groups : gs.key_cap * gs.n_groups;
-      if (blocks != want_blocks) throw Error(SDH_E_INVALID, "snapshot arena size mismatch");
-      get_dev(gs.a32.p, (size_t)blocks * e->gB32 * 64 * 4);
-      get_dev(gs.a64.p, (size_t)blocks * e->gB64 * 64 * 8);
-    }
-    if ((size_t)nx() != e->routes.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    for (auto& rp : e->routes) {
-      if (nx() != (rp ? 1 : 0)) throw Error(SDH_E_INVALID, "snapshot of a different program");
-      if (!rp) continue;
-      const size_t slots = (size_t)nx();
-      if (slots != (size_t)rp->tmask + 2) throw Error(SDH_E_INVALID, "snapshot key table mismatch");
-      get_dev(rp->tkey.p, slots * 8);
-      get_dev(rp->tid.p, slots * 4);
-      get_dev(rp->n_keys.p, 4);
-      get_dev(rp->key_of_id.p, (size_t)rp->max_keys * 8);
-      rp->kkind = (int)nx();
-      rp->nk_seen = nx();
-      const int64_t nko = nx();
-      if (nko < 0 || nko > rp->max_keys) throw Error(SDH_E_INVALID, "bad snapshot key order");
-      rp->korder_kid.resize((size_t)nko);
-      rp->korder_key.resize((size_t)nko);
-      for (int64_t j = 0; j < nko; ++j) {
-        rp->korder_kid[(size_t)j] = nx();
-        rp->korder_key[(size_t)j] = nx();
-      }
-      rp->fan.clear();
-    }
-    if ((size_t)nx() != e->psets.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    for (auto& pp : e->psets) {
-      auto& ps = *pp;
-      if (nx() != ps.partition || nx() != ps.kind) throw Error(SDH_E_INVALID, "snapshot of a different program");
-      const int64_t cap = nx(), key_cap = nx();
-      if (cap < 1 || cap > (1 << 20) || key_cap < 0 || key_cap > (int64_t)1 << 40)
-        throw Error(SDH_E_INVALID, "bad snapshot K_part table size");
-      ps.cap = (int)cap;
-      ps.key_cap = 0;
-      ps.st.n = 0;  // reallocated at the snapshot's capacity
-      if (ps.st.p) HIPCHK(hipFree(ps.st.p));
-      ps.st.p = nullptr;
-      part_grow(e, ps, key_cap);
-      if (ps.key_cap != key_cap) throw Error(SDH_E_INVALID, "snapshot key capacity mismatch");
-      get_dev(ps.st.p, (size_t)2 * ps.key_cap * ps.n_groups * ps.bw() * 64 * 8);
-      get_dev(ps.cur.p, (size_t)ps.key_cap * 4);
-    }
-    if ((size_t)nx() != e->seq_tail.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    for (size_t st = 0; st < e->seq_tail.size(); ++st) {
-      const int64_t tl = nx();
-      if (tl < 0 || tl > SEQ_TMAX) throw Error(SDH_E_INVALID, "bad snapshot tail length");
-      e->seq_tail_len[st] = (int32_t)tl;
-      get_dev(e->seq_tail[st].p, SEQ_TMAX * SEQ_TW * 8);
-    }
-    if ((size_t)nx() != e->ssets.size()) throw Error(SDH_E_INVALID, "snapshot of a different program");
-    for (auto& up : e->ssets) {
-      auto& ss = *up;
-      if (nx() != ss.partition) throw Error(SDH_E_INVALID, "snapshot of a different program");
-      const int64_t key_cap = nx(), ng = nx(), lds = nx(), words = nx();
-      if (ng != ss.n_groups || key_cap < 0 || key_cap > ((int64_t)1 << 32) || words < 0 || lds < 64 || lds > 13312)
-        throw Error(SDH_E_INVALID, "bad snapshot K_slab set");
-      ss.lds_words = (int)lds;
-      ss.key_cap = 0;
-      ss.dir.n = 0;
-      if (ss.dir.p) HIPCHK(hipFree(ss.dir.p));
-      ss.dir.p = nullptr;
-      slab_grow_keys(e, ss, key_cap);
-      if (ss.key_cap != key_cap) throw Error(SDH_E_INVALID, "snapshot key capacity mismatch");
-      get_dev(ss.dir.p, (size_t)key_cap * ng * 8);
-      DevBuf<uint32_t> packed;
-      packed.ensure(std::max<int64_t>(1, words));
-      get_dev(packed.p, (size_t)words * 4);
-      slab_init(e, ss, std::max<int64_t>(1 << 16, 2 * (words / ss.nsub) + 65536));
-      get_dev(ss.live.p, 256 * 8);
-      DevBuf<unsigned long long> zt;
-      DevBuf<uint32_t*> pr;
-      DevBuf<int64_t> pc;
-      zt.ensure(1);
-      pr.ensure(1);
-      pc.ensure(1);
-      const int64_t pcap = std::max<int64_t>(4, words);
-      HIPCHK(hipMemset(zt.p, 0, 8));
-      HIPCHK(hipMemcpy(pr.p, &packed.p, sizeof(uint32_t*), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(pc.p, &pcap, 8, hipMemcpyHostToDevice));
-      if (words && !slab_move_raw(e, ss, ss.dir.p, pr.p, pc.p, zt.p, 1, std::vector<unsigned long long>(1, ~0ull), {},
-                                  ss.d_ring.p, ss.d_cap.p, ss.head.p, ss.tail.p, ss.nsub))
-        throw Error(SDH_E_CAPACITY, "K_slab restore: a ring overflowed");
-      slab_heads(e, ss);
-      ss.h_push0 = ss.h_head;
-    }
-    // the event store: a retaining engine takes the snapshot's retained rows (those that fit its ring);
-    // a version-8 snapshot, or an engine that keeps no events, leaves the store empty
-    e->ev_first = e->seq;
-    if (version == SNAP_VERSION_EVENTS) {
-      const int64_t scap = nx(), sw = nx(), lo = nx();
-      const int64_t n = e->seq - lo;
-      if (scap < 1 || sw < 2 || sw > 2 + MAXATTR || lo < 0 || n < 0 || n > scap ||
-          (size_t)n * (size_t)sw > nw - i)
-        throw Error(SDH_E_INVALID, "bad snapshot event store");
-      if (e->ev_cap) {
-        if (sw != e->ev_w) throw Error(SDH_E_INVALID, "snapshot of a different program");
-        const int64_t keep = std::min(n, e->ev_cap), first = e->seq - keep;
-        i += (size_t)((n - keep) * sw);
-        const int64_t r0 = first & (e->ev_cap - 1), n0 = std::min(keep, e->ev_cap - r0);
-        get_dev(e->ev_rows.p + r0 * e->ev_w, (size_t)n0 * sw * 8);
-        get_dev(e->ev_rows.p, (size_t)(keep - n0) * sw * 8);
-        e->ev_first = first;
-      } else {
-        i += (size_t)(n * sw);
-      }
-    }
+    snap_load(e, snap::Reader(blob, len));
     e->g_dev_matches = 0;
     e->device_matches = 0;
     e->r_matches = 0;

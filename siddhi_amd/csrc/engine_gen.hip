@@ -228,6 +228,7 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
     r->n_keys.ensure(1);
     HIPCHK(hipMemset(r->n_keys.p, 0, 4));
     r->key_of_id.ensure(r->max_keys);
+    HIPCHK(hipMemset(r->key_of_id.p, 0, r->max_keys * 8));  // (a snapshot holds all of it: no stale device memory)
     r->track = !e->lp.parts[partition].fanout.empty();
     if (r->track && e->cfg.shard_world > 1)
       throw Error(SDH_E_UNSUPPORTED, "a non-partitioned stream inside a partition with key sharding");
@@ -1268,6 +1269,134 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
   e->stats.matches += (int64_t)nrec;
   e->g_dev_matches = (int64_t)nrec;
   e->g_used = (int64_t)used;
+}
+
+// ---- snapshot sections (engine_snap.hip): K_gen sets: instance arenas (Snapshotable state of every pre-processor of every instance)
+void snap_save_gen(sdh_engine* e, snap::Writer& w) {
+  w.put((int64_t)e->gsets.size());
+  for (auto& up : e->gsets) {
+    auto& gs = *up;
+    const int64_t blocks = gs.partition < 0 ? gs.n_groups : gs.key_cap * gs.n_groups;
+    w.put(gs.partition);
+    w.put(gs.key_cap);
+    w.put(blocks);
+    put_dev(w, gs.a32.p, (size_t)blocks * e->gB32 * 64 * 4);
+    put_dev(w, gs.a64.p, (size_t)blocks * e->gB64 * 64 * 8);
+  }
+}
+
+void snap_load_gen(sdh_engine* e, snap::Reader& r) {
+  snap::need((size_t)r.get() == e->gsets.size(), "snapshot of a different program");
+  for (auto& up : e->gsets) {
+    auto& gs = *up;
+    snap::need(r.get() == gs.partition, "snapshot of a different program");
+    const int64_t key_cap = r.get(), blocks = r.get();
+    if (gs.partition >= 0) {
+      gen_grow(e, gs, key_cap);
+      snap::need(gs.key_cap == key_cap, "snapshot key capacity mismatch");
+    }
+    snap::need(blocks == (gs.partition < 0 ? gs.n_groups : gs.key_cap * gs.n_groups), "snapshot arena size mismatch");
+    get_dev(r, gs.a32.p, (size_t)blocks * e->gB32 * 64 * 4);
+    get_dev(r, gs.a64.p, (size_t)blocks * e->gB64 * 64 * 8);
+  }
+}
+
+// partition key tables (PartitionRuntime's key -> instance map) and, for fan-out partitions, the keys'
+// creation order (the junction maps' insertion order)
+void snap_save_routes(sdh_engine* e, snap::Writer& w) {
+  w.put((int64_t)e->routes.size());
+  for (auto& rp : e->routes) {
+    w.put(rp ? 1 : 0);
+    if (!rp) continue;
+    const size_t slots = (size_t)rp->tmask + 2;
+    w.put((int64_t)slots);
+    put_dev(w, rp->tkey.p, slots * 8);
+    put_dev(w, rp->tid.p, slots * 4);
+    put_dev(w, rp->n_keys.p, 4);
+    put_dev(w, rp->key_of_id.p, (size_t)rp->max_keys * 8);
+    w.put(rp->kkind);
+    w.put(rp->nk_seen);
+    w.put((int64_t)rp->korder_kid.size());
+    for (size_t j = 0; j < rp->korder_kid.size(); ++j) {
+      w.put(rp->korder_kid[j]);
+      w.put(rp->korder_key[j]);
+    }
+  }
+}
+
+void snap_load_routes(sdh_engine* e, snap::Reader& r) {
+  snap::need((size_t)r.get() == e->routes.size(), "snapshot of a different program");
+  for (auto& rp : e->routes) {
+    snap::need(r.get() == (rp ? 1 : 0), "snapshot of a different program");
+    if (!rp) continue;
+    const size_t slots = (size_t)r.get();
+    snap::need(slots == (size_t)rp->tmask + 2, "snapshot key table mismatch");
+    get_dev(r, rp->tkey.p, slots * 8);
+    get_dev(r, rp->tid.p, slots * 4);
+    get_dev(r, rp->n_keys.p, 4);
+    get_dev(r, rp->key_of_id.p, (size_t)rp->max_keys * 8);
+    rp->kkind = (int)r.get();
+    rp->nk_seen = r.get();
+    const int64_t nko = r.get();
+    snap::need(nko >= 0 && nko <= rp->max_keys, "bad snapshot key order");
+    rp->korder_kid.resize((size_t)nko);
+    rp->korder_key.resize((size_t)nko);
+    for (size_t j = 0; j < (size_t)nko; ++j) {
+      rp->korder_kid[j] = r.get();
+      rp->korder_key[j] = r.get();
+    }
+    rp->fan.clear();
+  }
+}
+
+// K_part tables: both buffers and the per-key selector
+void snap_save_part(sdh_engine* e, snap::Writer& w) {
+  w.put((int64_t)e->psets.size());
+  for (auto& pp : e->psets) {
+    auto& ps = *pp;
+    w.put(ps.partition);
+    w.put(ps.kind);
+    w.put(ps.cap);
+    w.put(ps.key_cap);
+    put_dev(w, ps.st.p, (size_t)2 * ps.key_cap * ps.n_groups * ps.bw() * 64 * 8);
+    put_dev(w, ps.cur.p, (size_t)ps.key_cap * 4);
+  }
+}
+
+void snap_load_part(sdh_engine* e, snap::Reader& r) {
+  snap::need((size_t)r.get() == e->psets.size(), "snapshot of a different program");
+  for (auto& pp : e->psets) {
+    auto& ps = *pp;
+    snap::need(r.get() == ps.partition && r.get() == ps.kind, "snapshot of a different program");
+    const int64_t cap = r.get(), key_cap = r.get();
+    snap::need(cap >= 1 && cap <= (1 << 20) && key_cap >= 0 && key_cap <= (int64_t)1 << 40, "bad snapshot K_part table size");
+    ps.cap = (int)cap;
+    ps.key_cap = 0;
+    DevBuf<int64_t>().swap(ps.st);  // freed: reallocated at the snapshot's capacity
+    part_grow(e, ps, key_cap);
+    snap::need(ps.key_cap == key_cap, "snapshot key capacity mismatch");
+    get_dev(r, ps.st.p, (size_t)2 * ps.key_cap * ps.n_groups * ps.bw() * 64 * 8);
+    get_dev(r, ps.cur.p, (size_t)ps.key_cap * 4);
+  }
+}
+
+// K_seq: each stream's tail (the only state its windowed sequences carry between pushes)
+void snap_save_seq(sdh_engine* e, snap::Writer& w) {
+  w.put((int64_t)e->seq_tail.size());
+  for (size_t st = 0; st < e->seq_tail.size(); ++st) {
+    w.put(e->seq_tail_len[st]);
+    put_dev(w, e->seq_tail[st].p, SEQ_TMAX * SEQ_TW * 8);
+  }
+}
+
+void snap_load_seq(sdh_engine* e, snap::Reader& r) {
+  snap::need((size_t)r.get() == e->seq_tail.size(), "snapshot of a different program");
+  for (size_t st = 0; st < e->seq_tail.size(); ++st) {
+    const int64_t tl = r.get();
+    snap::need(tl >= 0 && tl <= SEQ_TMAX, "bad snapshot tail length");
+    e->seq_tail_len[st] = (int32_t)tl;
+    get_dev(r, e->seq_tail[st].p, SEQ_TMAX * SEQ_TW * 8);
+  }
 }
 
 }  // namespace eng

@@ -3,12 +3,14 @@
 // Everything here has hidden visibility: the library exports the C ABI (include/siddhi_hip.h) only.
 //
 //   engine.hip          the C ABI, knobs, sdh_engine_create (plan selection); the device match table and
-//                       its polls; pushes; the multi-GPU exchange; snapshot and restore
+//                       its polls; pushes; the multi-GPU exchange; the event store
 //   engine_gen.hip      the K_gen family (K_gen / K_seq / K_part / K_slab): sets and groups, arena and
 //                       table growth, the journal, partition routing and the launches of a push
 //   engine_lower.hip    IR reader, chain lowering, K_ratchet plan selection
 //   engine_ratchet.hip  K_chain and K_ratchet / K_gate / shared-pops launches
 //   engine_slab.hip     K_slab arena maintenance
+//   engine_snap.hip     the snapshot blob: format, prologue and the order of its sections, each a
+//                       snap_save_X / snap_load_X pair in the unit that owns that state
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,7 @@
 #include "nfa_types.h"
 #include "select_lower.h"
 #include "slab.h"
+#include "snap_io.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -605,7 +608,19 @@ inline void d2h_sync(sdh_engine* e, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipStreamSynchronize(e->stream));
 }
 
+// a device range into / out of a snapshot blob (snap_io.h)
+inline void put_dev(snap::Writer& w, const void* dptr, size_t bytes) {
+  void* to = w.bytes(bytes);
+  if (bytes) HIPCHK(hipMemcpy(to, dptr, bytes, hipMemcpyDeviceToHost));
+}
+inline void get_dev(snap::Reader& r, void* dptr, size_t bytes) {
+  const void* from = r.bytes(bytes);
+  if (bytes) HIPCHK(hipMemcpy(dptr, from, bytes, hipMemcpyHostToDevice));
+}
+
 // ---- functions that cross a unit boundary, by defining unit ----
+// engine.hip
+void snap_save_events(sdh_engine* e, snap::Writer& w), snap_load_events(sdh_engine* e, snap::Reader& r, bool stored);
 // engine_lower.hip
 IProgram read_ir(const void* blob, size_t len);
 Lowered lower_query(const IProgram& P, int qi);
@@ -620,25 +635,29 @@ void check_fan_strings(const sdh_engine* e, int stream);
 double gen_journal_bound(sdh_engine* e, int64_t n);
 void part_grow(sdh_engine* e, sdh_engine::PartSet& ps, int64_t keys);
 void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out, double* bytes_out);
+void snap_save_gen(sdh_engine* e, snap::Writer& w), snap_load_gen(sdh_engine* e, snap::Reader& r);
+void snap_save_routes(sdh_engine* e, snap::Writer& w), snap_load_routes(sdh_engine* e, snap::Reader& r);
+void snap_save_part(sdh_engine* e, snap::Writer& w), snap_load_part(sdh_engine* e, snap::Reader& r);
+void snap_save_seq(sdh_engine* e, snap::Writer& w), snap_load_seq(sdh_engine* e, snap::Reader& r);
 // engine_ratchet.hip
 void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
             const std::vector<int>& qs, bool allow_chunks, bool* unordered);
-void chain_grow(sdh_engine* e, int64_t want);
 void ratchet_build(sdh_engine* e, std::vector<std::pair<RatchetPlan, int>>& plans);
-void ratchet_grow_rsmax(sdh_engine* e, int64_t want);
 void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2]);
+void snap_save_chain(sdh_engine* e, snap::Writer& w), snap_load_chain(sdh_engine* e, snap::Reader& r, int64_t spcap);
+void snap_save_ratchet(sdh_engine* e, snap::Writer& w), snap_load_ratchet(sdh_engine* e, snap::Reader& r);
 // engine_slab.hip
 void slab_heads(sdh_engine* e, sdh_engine::SlabSet& ss);
 void slab_init(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t cap);
 void slab_grow_keys(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t keys);
-bool slab_move_raw(sdh_engine* e, sdh_engine::SlabSet& ss, uint64_t* dir, uint32_t* const* src_ring,
-                   const int64_t* src_cap, const unsigned long long* src_tail, int src_nsub,
-                   const std::vector<unsigned long long>& limit, const std::vector<uint8_t>& active,
-                   uint32_t* const* dst_ring, const int64_t* dst_cap, unsigned long long* dst_head,
-                   const unsigned long long* dst_tail, int dst_nsub, std::vector<uint8_t>* ring_fail = nullptr);
 void slab_prepare(sdh_engine* e, sdh_engine::SlabSet& ss, const std::vector<int64_t>* demand = nullptr);
 void slab_rollback(sdh_engine* e, sdh_engine::SlabSet& ss);
 int64_t slab_live_partials(sdh_engine* e, const sdh_engine::SlabSet& ss);
+int64_t slab_live_words(sdh_engine* e, const sdh_engine::SlabSet& ss);
+void snap_save_slab(sdh_engine* e, snap::Writer& w), snap_load_slab(sdh_engine* e, snap::Reader& r);
+// engine_snap.hip
+void snap_save(sdh_engine* e, snap::Writer& w);
+void snap_load(sdh_engine* e, snap::Reader r);
 
 }  // namespace eng
 }  // namespace sdh

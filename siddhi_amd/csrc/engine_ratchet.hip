@@ -8,7 +8,6 @@ namespace eng {
 namespace {
 int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
                     const std::vector<int>& qs, bool allow_chunks, bool* unordered);
-}
 
 // K_chain tables with room for `want` partials per query: both buffers re-laid on the device
 // ([q][field][pcap]: the field rows move, the new lanes are free). Up to 512 partials the sizes are
@@ -44,6 +43,7 @@ void chain_grow(sdh_engine* e, int64_t want) {
   e->chain_paged = e->chain_force_paged || cap > 512;
   ++e->chain_regrows;
 }
+}  // namespace
 
 // One K_chain step of the queries `qs` over batch B. A table overflow of a growing engine
 // (partials_per_inst == 0) is re-run here at a larger table: the kernels read part[cur] and write
@@ -283,6 +283,7 @@ void ratchet_build(sdh_engine* e, std::vector<std::pair<RatchetPlan, int>>& plan
   e->d_blk_next.ensure(4);
 }
 
+namespace {
 // persisted deques with room for `want` entries per lane: [g][rsmax][64] re-strided (both buffers)
 void ratchet_grow_rsmax(sdh_engine* e, int64_t want) {
   if (want <= e->rsmax) return;
@@ -299,8 +300,6 @@ void ratchet_grow_rsmax(sdh_engine* e, int64_t want) {
     }
   e->rsmax = cap;
 }
-
-namespace {
 
 int64_t ratchet_count_matches(sdh_engine* e) {
   int64_t n = 0;
@@ -758,6 +757,94 @@ void launch_ratchet(sdh_engine* e, int stream, const StreamBatch& B, const int64
     return;
   }
   throw Error(SDH_E_CAPACITY, "ratchet launch did not converge");
+}
+
+// ---- snapshot sections (engine_snap.hip): K_chain, per query its header and table
+void snap_save_chain(sdh_engine* e, snap::Writer& w) {
+  const size_t tbl = (size_t)NF * e->pcap;
+  for (size_t q = 0; q < e->lq.size(); ++q) {
+    InstHeader h;
+    HIPCHK(hipMemcpy(&h, e->d_hdr[e->cur[q]].p + q, sizeof h, hipMemcpyDeviceToHost));
+    w.put(h.seed_alive);
+    w.put(h.n_live);
+    put_dev(w, e->d_part[e->cur[q]].p + q * tbl, tbl * 8);
+  }
+}
+
+// (spcap: the snapshot's table capacity. A growing engine adopts larger tables; smaller ones load into
+// the lanes they have)
+void snap_load_chain(sdh_engine* e, snap::Reader& r, int64_t spcap) {
+  if (spcap > e->pcap) chain_grow(e, spcap);
+  const size_t tbl = (size_t)NF * e->pcap;
+  std::vector<int64_t> rows(tbl);
+  for (size_t q = 0; q < e->lq.size(); ++q) {
+    InstHeader h{(int32_t)r.get(), (int32_t)r.get(), 0, 0};
+    const int64_t* src = r.words((size_t)NF * spcap);
+    for (int f = 0; f < NF; ++f) {
+      int64_t* row = rows.data() + (size_t)f * e->pcap;
+      std::copy(src + (size_t)f * spcap, src + (size_t)(f + 1) * spcap, row);
+      std::fill(row + spcap, row + e->pcap, f == F_STATE ? -1 : 0);
+    }
+    HIPCHK(hipMemcpy(e->d_hdr[e->cur[q]].p + q, &h, sizeof h, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_part[e->cur[q]].p + q * tbl, rows.data(), tbl * 8, hipMemcpyHostToDevice));
+  }
+}
+
+// K_ratchet deques: per group, per lane: n then n x (ts0, seq, key)
+void snap_save_ratchet(sdh_engine* e, snap::Writer& w) {
+  const size_t ng = e->rg.size();
+  w.put((int64_t)ng);
+  for (size_t g = 0; g < ng; ++g) {
+    const int b = e->rcur[g];
+    RatchetState rs;
+    HIPCHK(hipMemcpy(&rs, e->d_rst[b].p + g, sizeof rs, hipMemcpyDeviceToHost));
+    std::vector<int64_t> t(e->rsmax * WAVE), sq(e->rsmax * WAVE), ky(e->rsmax * WAVE);
+    const size_t o = g * e->rsmax * WAVE;
+    HIPCHK(hipMemcpy(t.data(), e->d_rts[b].p + o, t.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sq.data(), e->d_rsq[b].p + o, sq.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ky.data(), e->d_rky[b].p + o, ky.size() * 8, hipMemcpyDeviceToHost));
+    for (int l = 0; l < WAVE; ++l) {
+      w.put(rs.n[l]);
+      for (int i = 0; i < rs.n[l]; ++i) {
+        w.put(t[i * WAVE + l]);
+        w.put(sq[i * WAVE + l]);
+        w.put(ky[i * WAVE + l]);
+      }
+    }
+  }
+}
+
+void snap_load_ratchet(sdh_engine* e, snap::Reader& r) {
+  const size_t ng = (size_t)r.get();
+  snap::need(ng == e->rg.size(), "snapshot of a different program");
+  // the persisted capacity grows to the longest deque first (a copy of the reader scans ahead for it)
+  int64_t longest = 0;
+  snap::Reader scan = r;
+  for (size_t k = 0; k < ng * WAVE; ++k) {
+    const int64_t nl = scan.get();
+    snap::need(nl >= 0 && nl <= ((int64_t)1 << 26) && 3 * (size_t)nl <= scan.left(), "bad snapshot deque length");
+    longest = std::max(longest, nl);
+    scan.skip(3 * (size_t)nl);
+  }
+  ratchet_grow_rsmax(e, longest);
+  for (size_t g = 0; g < ng; ++g) {
+    const int b = e->rcur[g];
+    RatchetState rs{};
+    std::vector<int64_t> t(e->rsmax * WAVE, 0), sq(e->rsmax * WAVE, 0), ky(e->rsmax * WAVE, 0);
+    for (int l = 0; l < WAVE; ++l) {
+      rs.n[l] = (int32_t)r.get();
+      for (int i = 0; i < rs.n[l]; ++i) {
+        t[i * WAVE + l] = r.get();
+        sq[i * WAVE + l] = r.get();
+        ky[i * WAVE + l] = r.get();
+      }
+    }
+    const size_t o = g * e->rsmax * WAVE;
+    HIPCHK(hipMemcpy(e->d_rst[b].p + g, &rs, sizeof rs, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_rts[b].p + o, t.data(), t.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_rsq[b].p + o, sq.data(), sq.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_rky[b].p + o, ky.data(), ky.size() * 8, hipMemcpyHostToDevice));
+  }
 }
 
 }  // namespace eng

@@ -76,13 +76,15 @@ void slab_grow_keys(sdh_engine* e, sdh_engine::SlabSet& ss, int64_t keys) {
   ss.key_cap = cap;
 }
 
+namespace {
+
 // One directory pass moving blocks (nfa_slab.hip slab_move_kernel); false if a destination ring
 // ran out of room (nothing is lost: a block keeps its old place until its directory word moves)
 bool slab_move_raw(sdh_engine* e, sdh_engine::SlabSet& ss, uint64_t* dir, uint32_t* const* src_ring,
                    const int64_t* src_cap, const unsigned long long* src_tail, int src_nsub,
                    const std::vector<unsigned long long>& limit, const std::vector<uint8_t>& active,
                    uint32_t* const* dst_ring, const int64_t* dst_cap, unsigned long long* dst_head,
-                   const unsigned long long* dst_tail, int dst_nsub, std::vector<uint8_t>* ring_fail) {
+                   const unsigned long long* dst_tail, int dst_nsub, std::vector<uint8_t>* ring_fail = nullptr) {
   DevBuf<unsigned long long> d_lim;
   DevBuf<uint8_t> d_act;
   d_lim.ensure(limit.size());
@@ -110,8 +112,6 @@ bool slab_move_raw(sdh_engine* e, sdh_engine::SlabSet& ss, uint64_t* dir, uint32
   HIPCHK(hipStreamSynchronize(e->stream));
   return err == 0;
 }
-
-namespace {
 
 // rings `which` into new buffers of new_cap[r] words holding their live blocks (a batch at a time,
 // so the extra memory is a batch's worth)
@@ -282,6 +282,17 @@ void slab_rollback(sdh_engine* e, sdh_engine::SlabSet& ss) {
   slab_heads(e, ss);
 }
 
+// the words of the set's live blocks (one pass over the directory)
+int64_t slab_live_words(sdh_engine* e, const sdh_engine::SlabSet& ss) {
+  DevBuf<unsigned long long> acc;
+  acc.ensure(1);
+  HIPCHK(hipMemsetAsync(acc.p, 0, 8, e->stream));
+  HIPCHK(sdh_slab_live_words(ss.dir.p, ss.key_cap * ss.n_groups, ss.n_groups, ss.d_group_ew.p, acc.p, e->stream));
+  unsigned long long w = 0;
+  d2h_sync(e, &w, acc.p, 8);
+  return (int64_t)w;
+}
+
 int64_t slab_live_partials(sdh_engine* e, const sdh_engine::SlabSet& ss) {
   long long v[256];
   HIPCHK(hipMemcpyAsync(v, ss.live.p, sizeof v, hipMemcpyDeviceToHost, e->stream));
@@ -289,6 +300,85 @@ int64_t slab_live_partials(sdh_engine* e, const sdh_engine::SlabSet& ss) {
   int64_t n = 0;
   for (long long x : v) n += x;
   return n;
+}
+
+// ---- snapshot section (engine_snap.hip): the live blocks packed into one ring, the directory pointing
+// into it, the counters ----
+namespace {
+// a one-ring arena over `buf` for slab_move_raw: the device's ring pointer and capacity words
+struct OneRing {
+  DevBuf<uint32_t*> ring;
+  DevBuf<int64_t> cap;
+  OneRing(const DevBuf<uint32_t>& buf, int64_t words) {
+    ring.ensure(1);
+    cap.ensure(1);
+    const int64_t c = std::max<int64_t>(4, words);
+    HIPCHK(hipMemcpy(ring.p, &buf.p, sizeof(uint32_t*), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(cap.p, &c, 8, hipMemcpyHostToDevice));
+  }
+};
+}  // namespace
+
+void snap_save_slab(sdh_engine* e, snap::Writer& w) {
+  w.put((int64_t)e->ssets.size());
+  for (auto& up : e->ssets) {
+    auto& ss = *up;
+    const int64_t n_dir = ss.key_cap * ss.n_groups;
+    DevBuf<unsigned long long> ph, pt;
+    ph.ensure(1);
+    pt.ensure(1);
+    HIPCHK(hipMemset(ph.p, 0, 8));
+    HIPCHK(hipMemset(pt.p, 0, 8));
+    const int64_t words = slab_live_words(e, ss);
+    DevBuf<uint64_t> dcopy;
+    DevBuf<uint32_t> packed;
+    dcopy.ensure(std::max<int64_t>(1, n_dir));
+    packed.ensure(std::max<int64_t>(1, words));
+    if (n_dir) HIPCHK(hipMemcpy(dcopy.p, ss.dir.p, n_dir * 8, hipMemcpyDeviceToDevice));
+    OneRing one(packed, words);
+    if (words && !slab_move_raw(e, ss, dcopy.p, ss.d_ring.p, ss.d_cap.p, ss.tail.p, ss.nsub,
+                                std::vector<unsigned long long>(ss.nsub, ~0ull), {}, one.ring.p, one.cap.p, ph.p, pt.p, 1))
+      throw Error(SDH_E_DEVICE, "K_slab snapshot: packing failed");
+    w.put(ss.partition);
+    w.put(ss.key_cap);
+    w.put(ss.n_groups);
+    w.put(ss.lds_words);
+    w.put(words);
+    put_dev(w, dcopy.p, (size_t)n_dir * 8);
+    put_dev(w, packed.p, (size_t)words * 4);
+    put_dev(w, ss.live.p, 256 * 8);
+  }
+}
+
+void snap_load_slab(sdh_engine* e, snap::Reader& r) {
+  snap::need((size_t)r.get() == e->ssets.size(), "snapshot of a different program");
+  for (auto& up : e->ssets) {
+    auto& ss = *up;
+    snap::need(r.get() == ss.partition, "snapshot of a different program");
+    const int64_t key_cap = r.get(), ng = r.get(), lds = r.get(), words = r.get();
+    snap::need(ng == ss.n_groups && key_cap >= 0 && key_cap <= ((int64_t)1 << 32) && words >= 0 && lds >= 64 && lds <= 13312,
+               "bad snapshot K_slab set");
+    ss.lds_words = (int)lds;
+    ss.key_cap = 0;
+    DevBuf<uint64_t>().swap(ss.dir);  // freed: reallocated at the snapshot's capacity
+    slab_grow_keys(e, ss, key_cap);
+    snap::need(ss.key_cap == key_cap, "snapshot key capacity mismatch");
+    get_dev(r, ss.dir.p, (size_t)key_cap * ng * 8);
+    DevBuf<uint32_t> packed;
+    packed.ensure(std::max<int64_t>(1, words));
+    get_dev(r, packed.p, (size_t)words * 4);
+    slab_init(e, ss, std::max<int64_t>(1 << 16, 2 * (words / ss.nsub) + 65536));
+    get_dev(r, ss.live.p, 256 * 8);
+    DevBuf<unsigned long long> zt;
+    zt.ensure(1);
+    HIPCHK(hipMemset(zt.p, 0, 8));
+    OneRing one(packed, words);
+    if (words && !slab_move_raw(e, ss, ss.dir.p, one.ring.p, one.cap.p, zt.p, 1, std::vector<unsigned long long>(1, ~0ull), {},
+                                ss.d_ring.p, ss.d_cap.p, ss.head.p, ss.tail.p, ss.nsub))
+      throw Error(SDH_E_CAPACITY, "K_slab restore: a ring overflowed");
+    slab_heads(e, ss);
+    ss.h_push0 = ss.h_head;
+  }
 }
 
 }  // namespace eng
