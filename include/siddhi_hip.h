@@ -264,7 +264,8 @@ int sdh_engine_poll_compact_ex(sdh_engine* e, int32_t device, sdh_matches_compac
  *
  * sdh_engine_poll_rows: the matches sdh_engine_poll would return, in its order, each projected through
  * its query's `select` list into one row of `width` cells (aggregations, group by and having are not on
- * this path: such apps are refused when they are planned). cells is column-major, cells[c * n + i] =
+ * this path: such apps are refused when they are planned; the built-in functions of siddhi_hip_ir.h run
+ * inside the outputs, and eventTimestamp() reads the row's ts). cells is column-major, cells[c * n + i] =
  * cell c of row i in the encoding above (0 under a null); bit c of nulls[i] is set when that cell is
  * null or c >= the number of outputs of query[i] (bits up to 63 alike). The window is consumed on
  * success only. Failures: SDH_E_INVALID without a prior sdh_engine_retain_events; SDH_E_UNSUPPORTED when

@@ -71,6 +71,31 @@
  *                         (ltype, rtype) -- false when either is null
  *   SDH_OP_ARITH          pop r, l; push l (imm = SDH_AR_*) r in restype (the widest of D > F > L > I);
  *                         division and modulo by zero give null
+ *
+ * Built-in functions (core/executor/function/*.java) lower to the ops below. They are evaluated
+ * eagerly: the reference is lazy for ifThenElse only (IfThenElseFunctionExecutor.execute(ComplexEvent)),
+ * and no instruction has a side effect or throws (/0 is null), so eager evaluation is equivalent.
+ *   SDH_OP_SELECT         pop else, then, cond; push then when cond is TRUE, else otherwise (a null
+ *                         cond takes the else branch, IfThenElseFunctionExecutor.java:93-100); restype
+ *                         is the type of both branches
+ *   SDH_OP_COALESCE       pop r, l; push l when l is non-null, r otherwise (CoalesceFunctionExecutor,
+ *                         DefaultFunctionExecutor); n-ary coalesce is a left fold
+ *   SDH_OP_CONVERT        pop x of ltype; push x converted to restype (ConvertFunctionExecutor.execute,
+ *                         CastFunctionExecutor.execute for int -> long): Java's narrowing -- float /
+ *                         double -> int / long saturate and NaN gives 0, long -> int wraps, -> float
+ *                         rounds to nearest, numeric -> bool is `== 1`, bool -> numeric 1 / 0; null
+ *                         stays null. Strings are never converted.
+ *   SDH_OP_MAX2           pop x of rtype, acc (a non-null double); push acc' = (double)x when x is
+ *                         non-null and (double)x > acc, acc otherwise -- one step of
+ *                         MaximumFunctionExecutor.execute(Object[]):101-121. maximum(x1..xn), n >= 2, is
+ *                         CONST Double.MIN_VALUE (the smallest positive double), then per argument its
+ *                         code and MAX2, then CONVERT double -> the arguments' type; with n == 1 it is
+ *                         the argument alone (FunctionExecutor.execute:101-102)
+ *   SDH_OP_MIN2           the same with `<` (MinimumFunctionExecutor); minimum's seed is Double.MAX_VALUE
+ *   SDH_OP_EVENT_TS       push the timestamp of the match's StateEvent as a long
+ *                         (EventTimestampFunctionExecutor.execute:70-72): what sdh_matches.ts /
+ *                         sdh_rows.ts carry. Selector outputs only: a filter's partial does not carry
+ *                         its StateEvent timestamp, and a program with it in a filter is refused.
  */
 #ifndef SIDDHI_HIP_IR_H
 #define SIDDHI_HIP_IR_H
@@ -96,6 +121,12 @@
 #define SDH_OP_OR 7
 #define SDH_OP_NOT 8
 #define SDH_OP_ARITH 9
+#define SDH_OP_SELECT 10
+#define SDH_OP_COALESCE 11
+#define SDH_OP_CONVERT 12
+#define SDH_OP_MAX2 13
+#define SDH_OP_MIN2 14
+#define SDH_OP_EVENT_TS 15
 #define SDH_CMP_EQ 0
 #define SDH_CMP_NE 1
 #define SDH_CMP_GT 2

@@ -362,7 +362,7 @@ int do_poll_rows(sdh_engine* e, sdh_rows* out, bool device) {
   const auto& S = e->selp;
   if (S.over >= 0)
     throw Error(SDH_E_UNSUPPORTED, fmt("query %d selects more than %d outputs", S.over, sel::MAXOUT));
-  if (S.bad) throw Error(SDH_E_INVALID, "a select list names a slot or an attribute its query lacks");
+  if (S.bad) throw Error(SDH_E_INVALID, "a select list names a slot or an attribute its query lacks, or holds an unknown opcode");
   if (S.max_depth > kg::GSTACK - 1)
     throw Error(SDH_E_UNSUPPORTED, "a select expression is too deep for the device evaluation stack");
   HIPCHK(hipSetDevice(e->dev));

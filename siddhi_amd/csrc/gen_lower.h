@@ -293,11 +293,10 @@ inline GQuery lower_gen(const LProgram& P, int qi, const Sizing& sz) {
           const auto& v = caps[q.st[in.a].stream];
           x.imm = std::find(v.begin(), v.end(), (int)in.imm) - v.begin();
         }
-        switch (in.op) {
-          case OP_CONST: case OP_ATTR: case OP_STREAM_IS_NULL: ++depth; break;
-          case OP_CMP: case OP_AND: case OP_OR: case OP_ARITH: --depth; break;
-          default: break;
-        }
+        const int dd = op_delta((int)in.op);
+        if (dd == OP_DELTA_BAD) throw LowerError("unknown opcode in a filter");
+        if (in.op == OP_EVENT_TS) throw LowerError("eventTimestamp() in a filter: a partial does not carry its StateEvent timestamp");
+        depth += dd;
         maxd = std::max(maxd, depth);
       }
       if (maxd >= GSTACK) throw LowerError("filter expression too deep");

@@ -51,7 +51,21 @@ constexpr int GMAXPOOL = 4096;   // StateEvents / nodes per instance after growt
 constexpr int VNODE = 0x7fff;
 
 enum { T_INT = 0, T_LONG, T_FLOAT, T_DOUBLE, T_BOOL, T_STRING };
-enum { OP_CONST = 1, OP_ATTR, OP_IS_NULL, OP_STREAM_IS_NULL, OP_CMP, OP_AND, OP_OR, OP_NOT, OP_ARITH };
+enum { OP_CONST = 1, OP_ATTR, OP_IS_NULL, OP_STREAM_IS_NULL, OP_CMP, OP_AND, OP_OR, OP_NOT, OP_ARITH,
+       // built-in functions (include/siddhi_hip_ir.h; core/executor/function/*.java)
+       OP_SELECT, OP_COALESCE, OP_CONVERT, OP_MAX2, OP_MIN2, OP_EVENT_TS };
+// net evaluation-stack entries of one instruction (OP_SELECT pops three and pushes one); OP_DELTA_BAD
+// for an opcode this build does not know -- every lowering refuses such a program
+constexpr int OP_DELTA_BAD = -100;
+KG_FN int op_delta(int op) {
+  switch (op) {
+    case OP_CONST: case OP_ATTR: case OP_STREAM_IS_NULL: case OP_EVENT_TS: return 1;
+    case OP_IS_NULL: case OP_NOT: case OP_CONVERT: return 0;
+    case OP_CMP: case OP_AND: case OP_OR: case OP_ARITH: case OP_COALESCE: case OP_MAX2: case OP_MIN2: return -1;
+    case OP_SELECT: return -2;
+    default: return OP_DELTA_BAD;
+  }
+}
 enum { CMP_EQ = 0, CMP_NE, CMP_GT, CMP_GE, CMP_LT, CMP_LE };
 enum { AR_ADD = 0, AR_SUB, AR_MUL, AR_DIV, AR_MOD };
 enum { K_STREAM = 0, K_COUNT, K_LOGICAL, K_ABSENT };  // K_ABSENT: AbsentStreamPre/PostStateProcessor
@@ -265,6 +279,69 @@ KG_FN Val arith(int op, int res, const Val& l, const Val& r) {
   return v;
 }
 
+// ---- built-in functions (core/executor/function/*.java) ----
+// Java's (int) / (long) of a double (JLS 5.1.3): NaN -> 0, out of range saturates, else truncation.
+// Range tests first: the C++ cast is undefined out of range.
+KG_FN int64_t j_d2i(double d) {
+  if (d != d) return 0;
+  if (d >= 2147483647.0) return INT32_MAX;
+  if (d <= -2147483648.0) return INT32_MIN;
+  return (int64_t)(int32_t)d;
+}
+KG_FN int64_t j_d2l(double d) {
+  if (d != d) return 0;
+  if (d >= 9223372036854775808.0) return INT64_MAX;
+  if (d <= -9223372036854775808.0) return INT64_MIN;
+  return (int64_t)d;
+}
+// ConvertFunctionExecutor.execute:126-231 for the non-string pairs (CastFunctionExecutor.execute:101-106
+// is its int -> long): the boxed .intValue() / .longValue() / .floatValue() / .doubleValue() are the
+// primitive casts, -> bool is `== 1`, bool -> numeric 1 / 0; null in -> null. x.type is the static
+// source type (the instruction's), so the dispatch is wave-uniform. A float source widens to double
+// exactly, so the narrowing is written once, over double.
+KG_FN Val convert(int to, const Val& x) {
+  Val v{to, x.null, 0};
+  if (x.null) return v;
+  const int from = x.type;
+  if (from == to) { v.bits = x.bits; return v; }
+  if (from == T_BOOL) {
+    const bool b = x.bits != 0;
+    v.bits = to == T_FLOAT ? bits_f(b ? 1.0f : 0.0f) : to == T_DOUBLE ? bits_d(b ? 1.0 : 0.0) : (b ? 1 : 0);
+    return v;
+  }
+  switch (to) {
+    case T_BOOL:
+      v.bits = (from == T_INT || from == T_LONG) ? (x.bits == 1) : (as_d(x) == 1.0);
+      break;
+    case T_INT: v.bits = from == T_LONG ? (int64_t)(int32_t)(uint32_t)(uint64_t)x.bits : j_d2i(as_d(x)); break;
+    case T_LONG: v.bits = from == T_INT ? (int64_t)(int32_t)x.bits : j_d2l(as_d(x)); break;
+    case T_FLOAT: v.bits = bits_f(as_f(x)); break;
+    default: v.bits = bits_d(as_d(x));
+  }
+  return v;
+}
+// one argument of Maximum / MinimumFunctionExecutor.execute(Object[]):101-121: the fold runs in
+// double; a null argument leaves `value` at the seed and NaN fails the strict compare, so neither wins
+KG_FN Val fold2(int op, const Val& acc, const Val& x) {
+  Val v{T_DOUBLE, 0, acc.bits};
+  if (x.null) return v;
+  const double a = d_of(acc.bits), d = as_d(x);
+  if (op == OP_MAX2 ? d > a : d < a) v.bits = bits_d(d);
+  return v;
+}
+// IfThenElseFunctionExecutor.execute:93-100: Boolean.TRUE.equals(cond) -- a null cond is the else branch
+KG_FN Val select3(int res, const Val& c, const Val& a, const Val& b) {
+  Val v = (!c.null && c.bits) ? a : b;
+  v.type = res;
+  return v;
+}
+// Coalesce / DefaultFunctionExecutor.execute: the first non-null
+KG_FN Val coalesce2(int res, const Val& l, const Val& r) {
+  Val v = l.null ? r : l;
+  v.type = res;
+  return v;
+}
+
 // Shape-compiled filters (spec.hip generates straight-line code from a shape's bytecode): one
 // helper per instruction kind, the instruction's static fields as template arguments, so every
 // type / operator dispatch of eval_code folds away at compile time. Same semantics, instruction
@@ -298,6 +375,20 @@ KG_FN Val sp_arith(Val l, Val r) {
   l.type = LT;
   r.type = RT;
   return arith(OP, RES, l, r);
+}
+template <int RES>
+KG_FN Val sp_select(const Val& c, const Val& a, const Val& b) { return select3(RES, c, a, b); }
+template <int RES>
+KG_FN Val sp_coalesce(const Val& l, const Val& r) { return coalesce2(RES, l, r); }
+template <int FROM, int TO>
+KG_FN Val sp_convert(Val x) {
+  x.type = FROM;
+  return convert(TO, x);
+}
+template <int OP, int XT>
+KG_FN Val sp_fold2(const Val& acc, Val x) {
+  x.type = XT;
+  return fold2(OP, acc, x);
 }
 KG_FN bool sp_true(const Val& v) { return !v.null && v.bits; }
 
@@ -364,6 +455,7 @@ KG_FN Val eval_insns_imm(const GInsn* code, Imm imm_of, int b, int e, Attr attr,
         break;
       }
       case OP_ATTR:
+      case OP_EVENT_TS:  // (the selector's attr() answers it from its match; filters never hold it: lower_gen)
         stk.push(attr(in));
         break;
       case OP_STREAM_IS_NULL:
@@ -403,6 +495,33 @@ KG_FN Val eval_insns_imm(const GInsn* code, Imm imm_of, int b, int e, Attr attr,
         l.type = in.lt;
         r.type = in.rt;
         stk.push(arith((int)in.imm, in.res, l, r));
+        break;
+      }
+      case OP_SELECT: {  // (three pops: RegStack stays at constant indices)
+        const Val b2 = stk.pop();
+        const Val a2 = stk.pop();
+        const Val c = stk.pop();
+        stk.push(select3(in.res, c, a2, b2));
+        break;
+      }
+      case OP_COALESCE: {
+        const Val r = stk.pop();
+        const Val l = stk.pop();
+        stk.push(coalesce2(in.res, l, r));
+        break;
+      }
+      case OP_CONVERT: {  // the source type is static, like OP_CMP's operand types
+        Val x = stk.pop();
+        x.type = in.lt;
+        stk.push(convert(in.res, x));
+        break;
+      }
+      case OP_MAX2:
+      case OP_MIN2: {
+        Val x = stk.pop();
+        const Val acc = stk.pop();
+        x.type = in.rt;
+        stk.push(fold2(in.op, acc, x));
         break;
       }
       default:
@@ -1492,10 +1611,8 @@ inline int seq_lookback(const GQuery& g) {
 inline int code_depth(const GQuery& g, int b, int e) {  // max evaluation-stack entries of a range
   int sp = 0, mx = 0;
   for (int pc = b; pc < e; ++pc) {
-    const int op = g.code[pc].op;
-    if (op == OP_CONST || op == OP_ATTR || op == OP_STREAM_IS_NULL) ++sp;
-    else if (op == OP_AND || op == OP_OR || op == OP_CMP || op == OP_ARITH) --sp;
-    else if (op != OP_IS_NULL && op != OP_NOT) ++sp;
+    const int d = op_delta(g.code[pc].op);
+    sp += d == OP_DELTA_BAD ? 1 : d;  // (lower_gen has refused unknown opcodes)
     mx = sp > mx ? sp : mx;
   }
   return mx;

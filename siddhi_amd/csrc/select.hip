@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void select_sorted_kernel(SelArgs A) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= A.n) return;
   const int32_t p = A.perm[i];
-  const sel::WordsMatch m{A.M.words + A.M.woff[p], A.M.wlen[p]};
+  const sel::WordsMatch m{A.M.words + A.M.woff[p], A.M.wlen[p], A.M.ts[p]};
   select_lane<DEEP>(A, i, (int)A.po_q[i], m);
 }
 
@@ -140,7 +140,8 @@ __global__ __launch_bounds__(256) void select_placed_kernel(SelArgs A) {
   sel::PairMatch m;
   m.e2 = A.seq_ref + (int64_t)d2;
   m.e1 = m.e2 - (int64_t)d1;
-  A.ots[i] = A.ts_log[d2];
+  m.ts = A.ts_log[d2];
+  A.ots[i] = m.ts;
   A.oseq[i] = m.e2;
   select_lane<DEEP>(A, i, q, m);
 }

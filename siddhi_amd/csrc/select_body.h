@@ -58,9 +58,11 @@ struct Tables {
 };
 
 // A match's slots. Words: the match table's form, per slot a count c then c event seqs.
+// (ts: the match's StateEvent timestamp, what OP_EVENT_TS reads)
 struct WordsMatch {
   const int64_t* w;
   int64_t len;
+  int64_t ts = 0;
   // the chain of `slot`: its length, and `at` = the index of its first seq in w
   KG_FN int64_t chain(int slot, int64_t& at) const {
     int64_t j = 0;
@@ -73,6 +75,7 @@ struct WordsMatch {
 // Pair: a K_ratchet match, two one-event slots {e1}, {e2} (a placed window's compact rows).
 struct PairMatch {
   int64_t e1, e2;
+  int64_t ts = 0;
   KG_FN int64_t chain(int slot, int64_t& at) const {
     at = slot;
     return slot < 2 ? 1 : 0;
@@ -98,6 +101,7 @@ enum { ERR_EVICTED = 1 };  // a referenced event has left the store
 template <class Match>
 KG_FN kg::Val attr_of(const Store& st, const Match& m, const kg::GInsn& in, int32_t& err) {
   kg::Val v{in.res, 1, 0};
+  if (in.op == kg::OP_EVENT_TS) return kg::Val{kg::T_LONG, 0, m.ts};  // EventTimestampFunctionExecutor.execute:70-72
   int64_t seq;
   // seq -1: the empty event an absent logical side borrows (StreamEventPool.borrowEvent), all null
   if (!event_of(m, in.a, in.b, seq) || seq < 0) return v;

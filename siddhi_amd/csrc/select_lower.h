@@ -83,11 +83,9 @@ inline Program lower_select(const kg::LProgram& P) {
           x.b = in.b;
           x.imm = in.op == kg::OP_CONST ? k++ : in.imm;
           S.code.push_back(x);
-          switch (in.op) {
-            case kg::OP_CONST: case kg::OP_ATTR: case kg::OP_STREAM_IS_NULL: ++depth; break;
-            case kg::OP_CMP: case kg::OP_AND: case kg::OP_OR: case kg::OP_ARITH: --depth; break;
-            default: break;
-          }
+          const int dd = kg::op_delta((int)in.op);
+          if (dd == kg::OP_DELTA_BAD) S.bad = true;  // an opcode this build does not know
+          else depth += dd;
           maxd = std::max(maxd, depth);
         }
         o.e = (int32_t)S.code.size();

@@ -138,6 +138,23 @@ std::string emit_filter(const kg::GQuery& g, int b, int e, const std::string& pr
         rhs = fmt("sdh::kg::sp_arith<%d, %d, %d, %d>(%s, %s)", (int)in.imm, in.res, in.lt, in.rt, l.c_str(), r.c_str());
         break;
       }
+      case kg::OP_SELECT: {
+        const std::string b2 = pop(), a2 = pop(), c = pop();
+        rhs = fmt("sdh::kg::sp_select<%d>(%s, %s, %s)", in.res, c.c_str(), a2.c_str(), b2.c_str());
+        break;
+      }
+      case kg::OP_COALESCE: {
+        const std::string r = pop(), l = pop();
+        rhs = fmt("sdh::kg::sp_coalesce<%d>(%s, %s)", in.res, l.c_str(), r.c_str());
+        break;
+      }
+      case kg::OP_CONVERT: rhs = fmt("sdh::kg::sp_convert<%d, %d>(%s)", in.lt, in.res, pop().c_str()); break;
+      case kg::OP_MAX2:
+      case kg::OP_MIN2: {
+        const std::string x = pop(), acc = pop();
+        rhs = fmt("sdh::kg::sp_fold2<%d, %d>(%s, %s)", in.op, in.rt, acc.c_str(), x.c_str());
+        break;
+      }
       default: rhs = "sdh::kg::Val{sdh::kg::T_BOOL, 1, 0}";
     }
     out += "    const sdh::kg::Val " + v + " = " + rhs + ";\n";

@@ -47,6 +47,8 @@ TYPE_NAME = {v: k for k, v in TYPE_CODE.items()}
 
 # bytecode ops
 OP_CONST, OP_ATTR, OP_IS_NULL, OP_STREAM_IS_NULL, OP_CMP, OP_AND, OP_OR, OP_NOT, OP_ARITH = range(1, 10)
+# built-in functions (include/siddhi_hip_ir.h): additions, function-free programs never carry them
+OP_SELECT, OP_COALESCE, OP_CONVERT, OP_MAX2, OP_MIN2, OP_EVENT_TS = range(10, 16)
 CMP_EQ, CMP_NE, CMP_GT, CMP_GE, CMP_LT, CMP_LE = range(6)
 CMP_CODE = {"==": CMP_EQ, "!=": CMP_NE, ">": CMP_GT, ">=": CMP_GE, "<": CMP_LT, "<=": CMP_LE}
 AR_ADD, AR_SUB, AR_MUL, AR_DIV, AR_MOD = range(5)

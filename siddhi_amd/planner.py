@@ -32,9 +32,10 @@ import struct
 from typing import List, Optional
 
 from . import chm, ql
-from .ir import (AR_CODE, CMP_CODE, INT_MAX, K_ABSENT, K_COUNT, K_LOGICAL, K_STREAM, L_AND, L_OR, N_COUNT,
+from .ir import (TYPE_NAME, AR_CODE, CMP_CODE, INT_MAX, K_ABSENT, K_COUNT, K_LOGICAL, K_STREAM, L_AND, L_OR, N_COUNT,
                  N_EVERY, N_LOGICAL, N_NEXT, N_STREAM, OP_AND, OP_ARITH, OP_ATTR, OP_CMP, OP_CONST,
-                 OP_IS_NULL, OP_NOT, OP_OR, OP_STREAM_IS_NULL, Q_PATTERN, Q_SEQUENCE, R_MULTI,
+                 OP_COALESCE, OP_CONVERT, OP_EVENT_TS, OP_IS_NULL, OP_MAX2, OP_MIN2, OP_NOT, OP_OR, OP_SELECT,
+                 OP_STREAM_IS_NULL, Q_PATTERN, Q_SEQUENCE, R_MULTI,
                  R_SINGLE, T_BOOL, T_DOUBLE, T_FLOAT, T_INT, T_LONG, T_STRING, TYPE_CODE, Insn,
                  ChainIR, NodeIR, OutputIR, PartitionIR, PartitionKeyIR, ProgramIR, QueryIR, ReceiverIR,
                  StateIR, StreamIR)
@@ -45,6 +46,34 @@ CURRENT = -1
 LAST = -2
 
 _NUMERIC = (T_INT, T_LONG, T_FLOAT, T_DOUBLE)
+
+# deepest evaluation stack the engine accepts (kgen.h GSTACK - 1; gen_lower.h and engine.hip refuse
+# deeper programs too -- the planner says so before a blob exists)
+MAX_STACK = 11
+
+_INSTANCE_OF = {"instanceOfInteger": T_INT, "instanceOfLong": T_LONG, "instanceOfFloat": T_FLOAT,
+                "instanceOfDouble": T_DOUBLE, "instanceOfBoolean": T_BOOL, "instanceOfString": T_STRING}
+# built-ins of the reference that stay off the accelerated path, and why
+_REFUSED_FUNCS = {
+    "currentTimeMillis": "it reads the host's clock",
+    "UUID": "it is not a function of the events",
+    "createSet": "object-typed values have no device form",
+    "sizeOfSet": "object-typed values have no device form",
+}
+
+
+def code_depth(code) -> int:
+    """Deepest evaluation stack of a postfix program (kgen.h kg::op_delta / kg::code_depth)."""
+    sp = mx = 0
+    for ins in code:
+        if ins.op in (OP_CONST, OP_ATTR, OP_STREAM_IS_NULL, OP_EVENT_TS):
+            sp += 1
+        elif ins.op == OP_SELECT:
+            sp -= 2
+        elif ins.op in (OP_CMP, OP_AND, OP_OR, OP_ARITH, OP_COALESCE, OP_MAX2, OP_MIN2):
+            sp -= 1
+        mx = max(mx, sp)
+    return mx
 
 
 def _f32_bits(v: float) -> int:
@@ -67,6 +96,10 @@ class _ExprCompiler:
     def compile(self, e) -> (List[Insn], int):
         code: List[Insn] = []
         t = self._emit(e, code)
+        # (function-free programs keep their path: the engine refuses a deep one when it is created)
+        if any(i.op >= OP_SELECT for i in code) and code_depth(code) > MAX_STACK:
+            raise SiddhiAppCreationException(
+                f"expression needs an evaluation stack of {code_depth(code)} entries, the engine has {MAX_STACK}")
         return code, t
 
     # --------------------------------------------------------------------------------------
@@ -133,7 +166,122 @@ class _ExprCompiler:
                     rtype = T_INT
                 code.append(Insn(OP_ARITH, ltype=lt, rtype=rt, restype=rtype, imm=AR_CODE[e.op]))
                 return rtype
+        if isinstance(e, ql.Func):
+            return self._emit_func(e, code)
         raise SiddhiAppCreationException(f"unsupported expression {e!r}")
+
+    # Built-in functions (ExpressionParser.java:397-440 builds an AttributeFunction's executor
+    # wherever it builds a compare's; core/executor/function/*.java). Arguments are evaluated
+    # eagerly: the reference is lazy for ifThenElse only, and no instruction has a side effect or
+    # throws (/0 is null), so the value is the same.
+    def _emit_func(self, e: "ql.Func", code) -> int:
+        name, n = e.name, len(e.args)
+
+        def bad(msg):
+            raise SiddhiAppCreationException(f"{name}(): {msg}")
+
+        if e.namespace is not None:
+            raise SiddhiAppCreationException(
+                f"function {e.namespace}:{name}() is an extension: extensions are outside the accelerated path")
+        if name in _REFUSED_FUNCS:
+            raise SiddhiAppCreationException(
+                f"function {name}() is outside the accelerated path: {_REFUSED_FUNCS[name]}")
+        if name == "eventTimestamp":      # EventTimestampFunctionExecutor.init:55-62, execute:70-72
+            if n != 0:
+                bad(f"required 0 parameters, but found {n}")
+            if self.current_state != UNKNOWN_STATE:
+                raise SiddhiAppCreationException(
+                    "eventTimestamp() in a filter is outside the accelerated path: inside a pattern it reads "
+                    "the partial's StateEvent timestamp, which the device plans do not carry (select lists "
+                    "evaluate it)")
+            code.append(Insn(OP_EVENT_TS, restype=T_LONG))
+            return T_LONG
+        if name == "ifThenElse":          # IfThenElseFunctionExecutor.init:63-88, execute:93-100
+            if n != 3:
+                bad(f"required only 3 arguments, but found {n}")
+            if self._emit(e.args[0], code) != T_BOOL:
+                bad("the condition should be of type BOOL")
+            t = self._emit(e.args[1], code)
+            if self._emit(e.args[2], code) != t:
+                bad("then and else should be of equivalent type")
+            code.append(Insn(OP_SELECT, restype=t))
+            return t
+        if name in ("coalesce", "default"):
+            if name == "default":         # DefaultFunctionExecutor.init:61-85
+                if n != 2:
+                    bad(f"requires 2 parameters (attribute, default value), but found {n}")
+                if not isinstance(e.args[1], ql.Const):
+                    bad("the default value must be a constant")
+            elif n == 0:                  # CoalesceFunctionExecutor.init:66-79
+                bad("must have at least one parameter")
+            t = self._emit(e.args[0], code)
+            for a in e.args[1:]:          # first non-null argument: a left fold
+                if self._emit(a, code) != t:
+                    bad("cannot have parameters with different type")
+                code.append(Insn(OP_COALESCE, restype=t))
+            return t
+        if name in ("maximum", "minimum"):  # Maximum/MinimumFunctionExecutor.init:63-92
+            if n == 0:
+                bad("needs at least one parameter")
+            if n == 1:                    # FunctionExecutor.execute:101-102 -> execute(Object): the argument
+                t = self._emit(e.args[0], code)
+                if t not in _NUMERIC:
+                    bad("parameters must be int, long, float or double")
+                return t
+            # execute(Object[]):101-133: a fold in double from Double.MIN_VALUE (the smallest POSITIVE
+            # double; minimum: Double.MAX_VALUE) that nulls and NaN never win, then (int)/(long)/(float)
+            seed = 4.9e-324 if name == "maximum" else 1.7976931348623157e308
+            code.append(Insn(OP_CONST, restype=T_DOUBLE, imm=_f64_bits(seed)))
+            t = None
+            for a in e.args:
+                at = self._emit(a, code)
+                if at not in _NUMERIC:
+                    bad("parameters must be int, long, float or double")
+                if t is not None and at != t:
+                    bad("all parameters should be of same type")
+                t = at
+                code.append(Insn(OP_MAX2 if name == "maximum" else OP_MIN2, ltype=T_DOUBLE, rtype=at,
+                                 restype=T_DOUBLE))
+            if t != T_DOUBLE:
+                code.append(Insn(OP_CONVERT, ltype=T_DOUBLE, restype=t))
+            return t
+        if name in ("convert", "cast"):   # ConvertFunctionExecutor.init:76-118, CastFunctionExecutor.init:66-98
+            if n != 2:
+                bad(f"required 2 parameters, but found {n}")
+            k = e.args[1]
+            if not (isinstance(k, ql.Const) and k.type == "string"):
+                bad("the second parameter must be a string constant naming a type")
+            to = TYPE_CODE.get(k.value.lower())
+            if to is None:
+                bad(f"the type must be one of int, long, float, double, bool, string, but found '{k.value}'")
+            t = self._emit(e.args[0], code)
+            if name == "cast":            # CastFunctionExecutor.execute:101-106: identity, int -> long widened
+                if t == to:
+                    return t
+                if (t, to) != (T_INT, T_LONG):
+                    bad(f"cast of {TYPE_NAME[t]} to {TYPE_NAME[to]}: the reference hands the value on unchanged "
+                        "and throws ClassCastException downstream")
+            elif t == to:                 # ConvertFunctionExecutor.execute:126-231 `return data`
+                return t
+            elif T_STRING in (t, to):
+                bad(f"convert of {TYPE_NAME[t]} to {TYPE_NAME[to]}: a string is a dictionary id on the device, "
+                    "string conversion is outside the accelerated path")
+            code.append(Insn(OP_CONVERT, ltype=t, restype=to))
+            return to
+        if name in _INSTANCE_OF:          # InstanceOf*FunctionExecutor: `data instanceof X`
+            if n != 1:
+                bad(f"required only 1 argument, but found {n}")
+            arg: List[Insn] = []
+            if self._emit(e.args[0], arg) != _INSTANCE_OF[name]:
+                code.append(Insn(OP_CONST, restype=T_BOOL, imm=0))
+            else:                         # the static type matches: true unless null
+                code.extend(arg)
+                code.append(Insn(OP_IS_NULL, restype=T_BOOL))
+                code.append(Insn(OP_NOT, restype=T_BOOL))
+            return T_BOOL
+        raise SiddhiAppCreationException(
+            f"function {name}() is not a built-in of the accelerated path (script functions and "
+            "extensions are refused)")
 
     @staticmethod
     def _check_compare(op, lt, rt):
@@ -383,6 +531,8 @@ def _walk_expr(e, fn):
         return ql.Not(_walk_expr(e.expr, fn))
     if isinstance(e, ql.BinOp):
         return ql.BinOp(e.op, _walk_expr(e.left, fn), _walk_expr(e.right, fn))
+    if isinstance(e, ql.Func):
+        return ql.Func(e.namespace, e.name, [_walk_expr(a, fn) for a in e.args])
     return e
 
 

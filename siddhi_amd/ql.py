@@ -21,8 +21,14 @@ Covers the part of the SiddhiQL grammar that feeds the pattern/sequence (NFA) pa
   (``e1=A and not B``, ``not A for T or e2=B``, ...; ``logical_absent_stateful_source``,
   ``SiddhiQL.g4:251-260``)
 
-Windows, joins, functions, group-by and output rate limiting are outside the accelerated path and
-raise :class:`SiddhiParserException`.
+* built-in functions ``name(arg, ...)`` wherever an expression stands, with an optional ``is null``
+  (``SiddhiQL.g4`` function_operation, null_check): ``ifThenElse``, ``coalesce``, ``default``,
+  ``maximum``, ``minimum``, ``convert``, ``cast``, ``instanceOf*``. The parser builds :class:`Func` for
+  any name, namespaced ones (``ns:fn``) included; the planner type-checks the built-ins above and
+  refuses every other function by name (planner.py ``_ExprCompiler._emit_func``).
+
+Windows, joins, group-by and output rate limiting are outside the accelerated path and raise
+:class:`SiddhiParserException`.
 """
 from __future__ import annotations
 
@@ -94,6 +100,14 @@ class BinOp:
     op: str            # 'and','or','==','!=','>','>=','<','<=','+','-','*','/','%'
     left: object
     right: object
+
+
+@dataclass
+class Func:
+    """``[namespace ':'] name '(' args ')'`` (AttributeFunction; SiddhiQL.g4 function_operation)."""
+    namespace: Optional[str]
+    name: str
+    args: List[object]
 
 
 # state elements -------------------------------------------------------------------------------
@@ -764,9 +778,27 @@ class Parser:
             return self.number()
         if t.kind in ("id", "kw"):
             if self.at("(", 1):
-                self.error("functions are outside the accelerated path")
+                self.i += 1
+                return self._maybe_is_null(self.function_call(None, t.text))
+            if self.at(":", 1) and self.peek(2).kind in ("id", "kw") and self.at("(", 3):
+                self.i += 3
+                return self._maybe_is_null(self.function_call(t.text, self.peek(-1).text))
             return self._maybe_is_null(self.attribute_or_stream_ref())
         self.error(f"unexpected token {t.text!r} in expression")
+
+    def function_call(self, namespace, name) -> Func:
+        """function_operation: (function_namespace ':')? function_id '(' attribute_list? ')'."""
+        self.expect("(")
+        args = []
+        if self.at("*") and self.at(")", 1):
+            self.error(f"{name}(*) is outside the accelerated path")
+        if not self.at(")"):
+            while True:
+                args.append(self.expression())
+                if not self.accept(","):
+                    break
+        self.expect(")")
+        return Func(namespace, name, args)
 
     def _maybe_is_null(self, e):
         if self.at("is"):

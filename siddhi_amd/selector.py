@@ -17,8 +17,8 @@ import numpy as np
 
 from .events import EventLog, StringDictionary, decode_value
 from .ir import (AR_ADD, AR_DIV, AR_MOD, AR_MUL, AR_SUB, CMP_EQ, CMP_GE, CMP_GT, CMP_LE, CMP_LT,
-                 CMP_NE, OP_AND, OP_ARITH, OP_ATTR, OP_CMP, OP_CONST, OP_IS_NULL, OP_NOT, OP_OR,
-                 OP_STREAM_IS_NULL, T_BOOL, T_DOUBLE, T_FLOAT, T_INT, T_LONG, T_STRING, Insn)
+                 CMP_NE, OP_AND, OP_ARITH, OP_ATTR, OP_CMP, OP_COALESCE, OP_CONST, OP_CONVERT, OP_EVENT_TS, OP_IS_NULL,
+                 OP_MAX2, OP_MIN2, OP_NOT, OP_OR, OP_SELECT, OP_STREAM_IS_NULL, T_BOOL, T_DOUBLE, T_FLOAT, T_INT, T_LONG, T_STRING, Insn)
 
 
 def _chain_at(chain: Sequence[int], idx: int):
@@ -108,7 +108,70 @@ def arith(op, res, lv, rv):
             return a / b
         except ZeroDivisionError:
             return None
+    if math.isinf(a) or math.isnan(a) or math.isnan(b):
+        return math.nan                # Java's % (JLS 15.17.3); math.fmod raises on an infinite dividend
     return math.fmod(a, b)
+
+
+# ---- built-in functions (core/executor/function/*.java), restated from the Java --------------
+def _j_d2i(d: float) -> int:
+    """Java (int) of a double (JLS 5.1.3): NaN -> 0, saturating, truncation toward zero."""
+    if d != d:
+        return 0
+    if d >= 2147483647.0:
+        return 2 ** 31 - 1
+    if d <= -2147483648.0:
+        return -2 ** 31
+    return int(d)
+
+
+def _j_d2l(d: float) -> int:
+    """Java (long) of a double: NaN -> 0, saturating, truncation toward zero."""
+    if d != d:
+        return 0
+    if d >= 9223372036854775808.0:
+        return 2 ** 63 - 1
+    if d <= -9223372036854775808.0:
+        return -2 ** 63
+    return int(d)
+
+
+def convert(v, frm: int, to: int):
+    """ConvertFunctionExecutor.execute:126-231 for the non-string pairs (and CastFunctionExecutor's
+    int -> long): Integer/Long/Float/Double .intValue() / .longValue() / .floatValue() /
+    .doubleValue() are Java's primitive casts; -> bool is `== 1`; bool -> numeric is 1 / 0."""
+    if v is None:
+        return None
+    if frm == to:
+        return v
+    if frm == T_BOOL:
+        one = 1 if v else 0
+        return {T_INT: one, T_LONG: one, T_FLOAT: np.float32(one), T_DOUBLE: float(one)}[to]
+    if to == T_BOOL:
+        return bool(v == 1)
+    if to == T_INT:
+        return _wrap(int(v), 32) if frm == T_LONG else _j_d2i(float(v))
+    if to == T_LONG:
+        return int(v) if frm == T_INT else _j_d2l(float(v))
+    if to == T_FLOAT:
+        if frm in (T_INT, T_LONG):
+            return np.int64(v).astype(np.float32)      # one rounding, to nearest
+        with np.errstate(all="ignore"):
+            return np.float32(v)
+    if to == T_DOUBLE:
+        return float(v)
+    raise ValueError(f"convert {frm} -> {to}")
+
+
+def fold_step(op, acc: float, v, t) -> float:
+    """One argument of Maximum/MinimumFunctionExecutor.execute(Object[]):101-121: a null argument
+    leaves `value` at the seed, which never passes the strict compare; nor does NaN."""
+    if v is None:
+        return acc
+    d = float(v)   # (double) of an int / long (to nearest even, as float(int)) / float (exact)
+    if op == OP_MAX2:
+        return d if d > acc else acc
+    return d if d < acc else acc
 
 
 def _const(ins: Insn, dictionary: StringDictionary, strings: List[str]):
@@ -125,8 +188,9 @@ def _const(ins: Insn, dictionary: StringDictionary, strings: List[str]):
 
 
 def evaluate(code: List[Insn], slots: Sequence[Sequence[int]], log: EventLog, stream_types,
-             dictionary: StringDictionary, strings: List[str]):
-    """Evaluate output bytecode over one match. Returns a Python value or None."""
+             dictionary: StringDictionary, strings: List[str], ts=None):
+    """Evaluate output bytecode over one match. Returns a Python value or None. `ts`: the match's
+    output timestamp (the StateEvent's, what eventTimestamp() reads)."""
     st = []   # (value, type)
     for ins in code:
         op = ins.op
@@ -161,14 +225,34 @@ def evaluate(code: List[Insn], slots: Sequence[Sequence[int]], log: EventLog, st
             r, rt = st.pop()
             l, lt = st.pop()
             st.append((arith(ins.imm, ins.restype, l, r), ins.restype))
+        elif op == OP_EVENT_TS:           # EventTimestampFunctionExecutor.execute:70-72
+            if ts is None:
+                raise ValueError("eventTimestamp() needs the match's timestamp (project(..., ts=))")
+            st.append((int(ts), T_LONG))
+        elif op == OP_SELECT:
+            b, _ = st.pop()
+            a, _ = st.pop()
+            c, _ = st.pop()
+            st.append((a if c is True else b, ins.restype))
+        elif op == OP_COALESCE:
+            r, _ = st.pop()
+            l, _ = st.pop()
+            st.append((r if l is None else l, ins.restype))
+        elif op == OP_CONVERT:
+            v, _ = st.pop()
+            st.append((convert(v, ins.ltype, ins.restype), ins.restype))
+        elif op in (OP_MAX2, OP_MIN2):
+            v, _ = st.pop()
+            acc, _ = st.pop()
+            st.append((fold_step(op, acc, v, ins.rtype), T_DOUBLE))
         else:
             raise ValueError(f"bad opcode {op}")
     v, t = st[-1]
     return v
 
 
-def project(query_ir, match_slots, log: EventLog, stream_types, dictionary, strings):
-    return [evaluate(o.code, match_slots, log, stream_types, dictionary, strings)
+def project(query_ir, match_slots, log: EventLog, stream_types, dictionary, strings, ts=None):
+    return [evaluate(o.code, match_slots, log, stream_types, dictionary, strings, ts)
             for o in query_ir.outputs]
 
 
@@ -213,5 +297,5 @@ def stream_rows(ir, matches, log: EventLog, dictionary, strings, stream: str) ->
 
     for m in matches:
         q = ir.queries[m[0]]
-        deliver(project(q, m[3], log, None, dictionary, strings), [o.type for o in q.outputs], q.output_stream)
+        deliver(project(q, m[3], log, None, dictionary, strings, m[2]), [o.type for o in q.outputs], q.output_stream)
     return out
