@@ -82,6 +82,11 @@ typedef struct sdh_config {
    *          (StreamPreStateProcessor.java:59-60); the only limit is device memory;
    *   n > 0  a fixed capacity the caller chose: 64, 128, 256 or 512 (n rounded up; larger values
    *          mean 512). A push that needs more fails with SDH_E_CAPACITY.
+   * K_chain takes a chain whose filters are built from compares, and / or / not, is null and
+   * arithmetic over the current event and the earlier slots: what is not a plain compare of two
+   * operands runs as a residual program per event or per (partial, event) (DESIGN.md §3.2 "General
+   * predicates"; functions and stream-null tests in a filter keep a query on K_gen). An engine that
+   * holds such a query pages its tables past 256 partials instead of 512.
    * sdh_engine_restore: a growing engine adopts the snapshot's capacity; a fixed engine takes
    * snapshots of its own capacity only (SDH_E_INVALID otherwise).                               */
   int32_t partials_per_inst;
@@ -200,7 +205,8 @@ typedef struct sdh_stats {
                              /* rows (no sort at poll; matches.hip ratchet_place_kernel)          */
   int64_t plan_queries[8];   /* queries (pattern instances of this shard) per device plan:         */
                              /* [0] K_ratchet [1] K_gate [2] K_chain [3] K_part [4] K_slab         */
-                             /* [5] K_seq [6] K_gen                                */
+                             /* [5] K_seq [6] K_gen. [2] counts the chains with    */
+                             /* or / not / is null / arithmetic filters too (residual programs)   */
 } sdh_stats;
 
 int sdh_engine_create(const void* ir_blob, size_t len, const sdh_config* cfg, sdh_engine** out);

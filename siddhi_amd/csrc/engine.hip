@@ -1316,7 +1316,7 @@ int sdh_engine_create(const void* ir, size_t len, const sdh_config* cfg, sdh_eng
       // q % world); a partition's queries run on every rank, each rank owning the keys that
       // key_shard maps to it (nfa_gen.hip: foreign keys' events are dropped at routing)
       if (e->lp.q[qi].partition < 0 && qi % e->cfg.shard_world != e->cfg.shard_rank) continue;
-      Lowered L = force_gen ? Lowered() : lower_query(e->prog, qi);
+      Lowered L = force_gen ? Lowered() : lower_chain(e->prog, qi);
       if (!L.ok) {
         gen_qs.push_back(qi);
         continue;
@@ -1345,8 +1345,23 @@ int sdh_engine_create(const void* ir, size_t len, const sdh_config* cfg, sdh_eng
     HIPCHK(hipEventCreate(&e->ev_h1));
     for (auto& ev : e->ev_stage) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     e->d_q.ensure(std::max<size_t>(1, e->lq.size()));
+    // the queries' residual programs in one device table: each query's ranges rebased into it
     std::vector<ChainQuery> cqs;
-    for (auto& L : e->lq) cqs.push_back(L.cq);
+    std::vector<kg::GInsn> rcode;
+    for (auto& L : e->lq) {
+      const int base = (int)rcode.size();
+      for (int s = 0; s < MAXS; ++s) {
+        L.cq.rt_b[s] += base; L.cq.rt_e[s] += base;
+        L.cq.rp_b[s] += base; L.cq.rp_e[s] += base;
+      }
+      rcode.insert(rcode.end(), L.rcode.begin(), L.rcode.end());
+      cqs.push_back(L.cq);
+    }
+    e->chain_resid = !rcode.empty();
+    e->chain_paged = e->chain_force_paged || e->pcap > chain_reg_limit(e);
+    e->d_rcode.ensure(std::max<size_t>(1, rcode.size()));
+    if (!rcode.empty())
+      HIPCHK(hipMemcpy(e->d_rcode.p, rcode.data(), rcode.size() * sizeof(kg::GInsn), hipMemcpyHostToDevice));
     if (!cqs.empty())
       HIPCHK(hipMemcpy(e->d_q.p, cqs.data(), cqs.size() * sizeof(ChainQuery), hipMemcpyHostToDevice));
     ensure_state(e);

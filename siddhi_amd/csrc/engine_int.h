@@ -6,7 +6,7 @@
 //                       its polls; pushes; the multi-GPU exchange; the event store
 //   engine_gen.hip      the K_gen family (K_gen / K_seq / K_part / K_slab): sets and groups, arena and
 //                       table growth, the journal, partition routing and the launches of a push
-//   engine_lower.hip    IR reader, chain lowering, K_ratchet plan selection
+//   engine_lower.hip    the callers of the host-side lowerings (chain_lower.h, select_lower.h)
 //   engine_ratchet.hip  K_chain and K_ratchet / K_gate / shared-pops launches
 //   engine_slab.hip     K_slab arena maintenance
 //   engine_snap.hip     the snapshot blob: format, prologue and the order of its sections, each a
@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/siddhi_hip.h"
+#include "chain_lower.h"
 #include "comm.h"
 #include "knobs.h"
 #include "gen_lower.h"
@@ -48,76 +49,13 @@ struct Error : std::runtime_error {
   Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 
-inline std::string fmt(const char* f, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, f);
-  vsnprintf(buf, sizeof buf, f, ap);
-  va_end(ap);
-  return buf;
-}
-
 #define HIPCHK(x)                                                                         \
   do {                                                                                    \
     hipError_t e_ = (x);                                                                  \
     if (e_ != hipSuccess) throw Error(SDH_E_DEVICE, fmt("%s: %s", #x, hipGetErrorString(e_))); \
   } while (0)
 
-// the IR as read (format: siddhi_amd/ir.py)
-struct Insn {
-  int op, lt, rt, res;
-  int64_t a, b, imm;
-};
-struct IState {
-  int kind, stream, is_start, min, max, ltype, partner, next_pre, next_every, within_every, callback,
-      this_last, has_selector;
-  int64_t waiting;  // absent states: the 'for' time (ms), else -1
-  std::vector<std::vector<Insn>> filters;
-};
-struct IQuery {
-  int type, partition;
-  int64_t within;
-  std::vector<IState> st;
-};
-struct IProgram {
-  std::vector<std::vector<int>> stream_types;
-  std::vector<IQuery> q;
-};
-
-// lowering (engine_lower.hip): a filter's expression tree node, and a query lowered to a ChainQuery
-struct Node {
-  int kind;  // 0 leaf operand, 1 cmp, 2 and, 3 other
-  Insn ins;
-  int l = -1, r = -1;
-};
-
-struct Lowered {
-  bool ok = false;
-  std::string why;
-  ChainQuery cq{};
-  std::vector<int> streams;
-};
-
-// K_ratchet plan of a query (ratchet_plan)
-struct RatchetPlan {
-  bool ok = false;
-  int stream = 0, key_attr = 0, key_conv = 0, key_kind = 0, xmask = 0;
-  std::vector<RatchetAtom> f0;
-  std::vector<int64_t> f0c;
-  // K_gate (nfa_gate.hip): e2's event-only conjuncts `cur.b OP const` (empty: plain K_ratchet)
-  std::vector<RatchetAtom> g;
-  std::vector<int64_t> gc;
-  int64_t within = -1;
-  // grouping signature: everything except the per-lane constants and `within`
-  std::vector<int64_t> sig() const {
-    std::vector<int64_t> v{stream, key_kind, key_attr, key_conv, xmask, within >= 0, (int64_t)f0.size(),
-                           (int64_t)g.size()};
-    for (const auto* atoms : {&f0, &g})
-      for (const auto& a : *atoms)
-        v.insert(v.end(), {a.attr, a.conv, a.cur_left, a.mask, a.f64, a.cur2, a.attr2, a.conv2});
-    return v;
-  }
-};
+// (the IR as read, a query lowered to a ChainQuery, the K_ratchet plan, fmt: chain_lower.h)
 
 // SDH_ALLOC_TRACE=1: one stderr line per device buffer (re)allocation (p99 push/poll latency hunts)
 inline void alloc_trace(const char* what, size_t bytes) {
@@ -230,6 +168,8 @@ struct sdh_engine {
   int64_t chain_regrows = 0;         // table growths so far (sdh_stats.pool_regrows)
   DevBuf<int64_t> d_pscratch;
   DevBuf<ChainQuery> d_q;
+  DevBuf<kg::GInsn> d_rcode;         // the K_chain queries' residual programs (chain_pred.h), one table
+  bool chain_resid = false;          // a K_chain query has one: the R = true kernels run
   DevBuf<InstHeader> d_hdr[2];
   DevBuf<int64_t> d_part[2];
   std::vector<int> cur;              // which buffer holds each local query's state
@@ -602,6 +542,11 @@ struct sdh_engine {
 namespace sdh {
 namespace eng {
 
+// the most partials per query the register forms of K_chain hold; past it the tables are paged. With
+// a residual program in the engine that is 256: the eight-set R = true form of a chain of two or more
+// states does not fit the registers without private memory, so it is not built
+inline int chain_reg_limit(const sdh_engine* e) { return e->chain_resid ? 256 : 512; }
+
 // a small device value the host decides on: copied over the engine's stream, which is then drained
 inline void d2h_sync(sdh_engine* e, void* dst, const void* src, size_t bytes) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
@@ -623,9 +568,8 @@ inline void get_dev(snap::Reader& r, void* dptr, size_t bytes) {
 void snap_save_events(sdh_engine* e, snap::Writer& w), snap_load_events(sdh_engine* e, snap::Reader& r, bool stored);
 // engine_lower.hip
 IProgram read_ir(const void* blob, size_t len);
-Lowered lower_query(const IProgram& P, int qi);
+Lowered lower_chain(const IProgram& P, int qi);
 int attr_width(int t);
-RatchetPlan ratchet_plan(const ChainQuery& c);
 sel::Program lower_outputs(const kg::LProgram& P);
 // engine_gen.hip
 void gen_build(sdh_engine* e, const std::vector<int>& qis);

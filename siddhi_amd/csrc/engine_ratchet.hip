@@ -40,7 +40,7 @@ void chain_grow(sdh_engine* e, int64_t want) {
   }
   e->pcap = (int)cap;
   e->K = cap <= 64 ? 1 : cap <= 128 ? 2 : cap <= 256 ? 4 : 8;
-  e->chain_paged = e->chain_force_paged || cap > 512;
+  e->chain_paged = e->chain_force_paged || cap > chain_reg_limit(e);
   ++e->chain_regrows;
 }
 }  // namespace
@@ -151,6 +151,7 @@ int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64
   L.seg_count = e->d_seg_count.p;
   L.err = e->d_err.p;
   L.scratch = e->d_pscratch.p;
+  L.rcode = e->d_rcode.p;
   const size_t lds = 0;
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   for (int i0 = 0; i0 < n_items;) {
@@ -161,8 +162,8 @@ int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64
     Ls.work = e->d_work.p + i0;
     Ls.seg_count = e->d_seg_count.p + i0;
     Ls.n_work = i1 - i0;
-    if (paged(e->work[i0].q)) HIPCHK(sdh_launch_chain_paged(S, &Ls, (Ls.n_work + 3) / 4, e->stream));
-    else HIPCHK(sdh_launch_chain(S, e->K, &Ls, (Ls.n_work + 3) / 4, lds, e->stream));
+    if (paged(e->work[i0].q)) HIPCHK(sdh_launch_chain_paged(S, e->chain_resid, &Ls, (Ls.n_work + 3) / 4, e->stream));
+    else HIPCHK(sdh_launch_chain(S, e->K, e->chain_resid, &Ls, (Ls.n_work + 3) / 4, lds, e->stream));
     i0 = i1;
   }
   HIPCHK(hipEventRecord(e->ev1, e->stream));

@@ -74,9 +74,11 @@ extern "C" hipError_t sdh_gen_remap(const int32_t* lane_q, int group_base, int n
                                     const int64_t* o64, int64_t oB32, int64_t oB64, int32_t* n32, int64_t* n64,
                                     int64_t nB32, int64_t nB64, hipStream_t s);
 
-extern "C" hipError_t sdh_launch_chain(int n_states, int k, const sdh::ChainLaunch* L, int n_blocks,
+// (resid: a query of the engine has a residual program -- the R = true instantiations)
+extern "C" hipError_t sdh_launch_chain(int n_states, int k, int resid, const sdh::ChainLaunch* L, int n_blocks,
                                        size_t lds, hipStream_t s);
-extern "C" hipError_t sdh_launch_chain_paged(int n_states, const sdh::ChainLaunch* L, int n_blocks, hipStream_t s);
+extern "C" hipError_t sdh_launch_chain_paged(int n_states, int resid, const sdh::ChainLaunch* L, int n_blocks,
+                                             hipStream_t s);
 extern "C" hipError_t sdh_chain_relayout(const int64_t* src, int64_t* dst, int64_t rows, int old_cap, int new_cap,
                                          hipStream_t s);
 extern "C" hipError_t sdh_launch_ratchet(int key_kind, int xmask, int full, int nf, int sim, int ML, int SC,

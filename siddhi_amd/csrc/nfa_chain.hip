@@ -14,7 +14,9 @@
 //     re-arms a shallow clone); without `every` the seed is consumed by its first match (R3)
 //   * the last state emits (isEventReturned, :310-313) and drops the partial (stateChanged)
 //   * predicates: conjunctions of typed compares, null -> false (FilterProcessor:55-66,
-//     CompareConditionExpressionExecutor:39-43), evaluated in Java's promotion domain
+//     CompareConditionExpressionExecutor:39-43), evaluated in Java's promotion domain; conjuncts that
+//     are more than a compare of two operands (or / not / is null / arithmetic) run as residual
+//     programs through kgen.h's stack machine (chain_pred.h; the R = true kernels)
 //
 // Mapping to CDNA4: one 64-lane wave owns one (query instance, event chunk); each lane holds one
 // partial match in registers (K register sets -> 64*K partials). Every 64 events the wave stages
@@ -30,7 +32,8 @@
 // has expired by event c0-1. Requires non-decreasing timestamps, which every wave verifies on
 // the range it reads (err[1]); the host re-runs the batch unchunked otherwise.
 //
-// Paged form (nfa_chain_paged_kernel; more than 512 partials per query, or SDH_CHAIN_PAGED): the
+// Paged form (nfa_chain_paged_kernel; more than 512 partials per query -- 256 in an engine with a
+// residual program, engine_int.h chain_reg_limit -- or SDH_CHAIN_PAGED): the
 // reference's pending lists are unbounded (StreamPreStateProcessor.java:59-60, :203-216, walked in
 // full at :298) and registers end at 64 * 8 partials, so past that the table stays in HBM, same
 // field-major layout, in pages of 64 entries (one coalesced load per field). The walk is entry-major
@@ -62,6 +65,7 @@
 // re-runs the push once at a size that fits -- part[inb] is read, never written, until then.
 #include <hip/hip_runtime.h>
 
+#include "chain_pred.h"
 #include "launchers.h"
 #include "nfa_types.h"
 
@@ -166,7 +170,8 @@ __device__ int64_t lower_bound_ts(const int64_t* ts, int64_t c0, int64_t target,
 // loop carries no data-dependent decisions about the query's shape.
 struct StateDesc {
   int active;        // state fed by this launch's stream
-  int has_x;         // state has a capture-reading atom (at most one, planner-enforced)
+  int has_x;         // state has a capture-reading atom (at most one: chain_lower.h sends a state's
+                     // further capture readers to its partial residual)
   int l_cap, r_cap;  // operand is a captured value (index in lcap/rcap)
   int l_cur, r_cur;  // operand is the current event (key in xcur)
   int lcap, rcap;
@@ -174,9 +179,38 @@ struct StateDesc {
   int l_null, r_null;
   int f64, mask;
   uint32_t capmask;  // captures taken when a partial passes this state
+  int rp_b, rp_e;    // R kernels: the state's partial residual, instructions [rp_b, rp_e) of rcode
 };
 
-template <int S, int K>
+// The residual hooks of the R = true kernels (chain_pred.h). Tile residual, lane = event: the lane's
+// own raw column words and null bits. Partial residual, lane = partial: the current event's words are
+// wave-uniform (readlane of the staged column at k), the captures the lane's own. partial_residual is
+// called with every lane active: lane k computes the word the others read from it.
+template <class ColKey>
+__device__ __forceinline__ bool tile_residual(const kg::GInsn* code, int b, int e, const ColKey& col_key, uint32_t cnul) {
+  return cpred::residual_pass(
+      code, b, e, [&](int c, bool& nul) { nul = (cnul >> c) & 1u; return col_key(c); },
+      [](int, bool& nul) { nul = true; return (int64_t)0; });
+}
+// (a partial's captures as named words, by value: an array behind a reference stays in private memory)
+struct Caps {
+  int64_t c0, c1, c2, c3;
+  uint32_t cn;
+};
+static_assert(MAXCAP == 4, "Caps names the captures");
+__device__ __forceinline__ Caps caps_of(const PSet& P) { return Caps{P.cp[0], P.cp[1], P.cp[2], P.cp[3], P.cn}; }
+template <class ColKey>
+__device__ __forceinline__ bool partial_residual(const kg::GInsn* code, int b, int e, const ColKey& col_key,
+                                                 const uint32_t cnul_k, const int k, const Caps C) {
+  return cpred::residual_pass(
+      code, b, e, [&](int c, bool& nul) { nul = (cnul_k >> c) & 1u; return readlane64(col_key(c), k); },
+      [&](int c, bool& nul) {
+        nul = (C.cn >> c) & 1u;
+        return c == 1 ? C.c1 : c == 2 ? C.c2 : c == 3 ? C.c3 : C.c0;
+      });
+}
+
+template <int S, int K, bool R>
 __global__ __launch_bounds__(256) void nfa_chain_kernel(ChainLaunch L) {
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -207,6 +241,10 @@ __global__ __launch_bounds__(256) void nfa_chain_kernel(ChainLaunch L) {
     uint32_t cm = 0;
     for (int c = 0; c < n_cap; ++c) cm |= (Q->cap_slot[c] == s ? 1u : 0u) << c;
     d.capmask = cm;
+    if constexpr (R) {
+      d.rp_b = Q->rp_b[s];
+      d.rp_e = Q->rp_e[s];
+    }
     D[s] = d;
   }
 
@@ -303,6 +341,10 @@ __global__ __launch_bounds__(256) void nfa_chain_kernel(ChainLaunch L) {
             xnul |= ((cnul >> col) & 1u) << s;
           }
         }
+        if constexpr (R) {
+          const int rb = Q->rt_b[s], re = Q->rt_e[s];
+          if (re > rb) ok = ok && tile_residual(L.rcode, rb, re, col_key, cnul);
+        }
       }
       smask[s] = __ballot(ok);
     }
@@ -331,6 +373,7 @@ __global__ __launch_bounds__(256) void nfa_chain_kernel(ChainLaunch L) {
       const int64_t cseq = L.b.seq_base + j;
       const uint32_t capn_k = __builtin_amdgcn_readlane(capn, k);
       const uint32_t xnul_k = __builtin_amdgcn_readlane(xnul, k);
+      const uint32_t cnul_k = R ? __builtin_amdgcn_readlane(cnul, k) : 0u;
 
       // ---- non-start states, last to first (reverse registration order) ----
 #pragma unroll
@@ -341,20 +384,56 @@ __global__ __launch_bounds__(256) void nfa_chain_kernel(ChainLaunch L) {
         const bool cpass = (smask[s] >> k) & 1ull;
         const int64_t cur = readlane64(xcur[s], k);
         const bool curn = (xnul_k >> s) & 1u;
-#pragma unroll
-        for (int kk = 0; kk < K; ++kk) {
-          const bool in_s = P[kk].st == s;
-          if (__ballot(in_s) == 0) continue;
-          const bool exp = in_s && expired(P[kk].ts0, cts, within);
+        // the state's test of one partial before its residual: in the state, not expired, the event
+        // passes the tile mask, the capture-reading atom holds
+        auto atoms_pass = [&](const PSet& Pk, bool& exp) __attribute__((always_inline)) {
+          const bool in_s = Pk.st == s;
+          exp = in_s && expired(Pk.ts0, cts, within);
           bool pass = in_s && !exp && cpass;
           if (d.has_x) {
-            const int64_t lcap = cap_get(P[kk], d.lcap), rcap = cap_get(P[kk], d.rcap);
+            const int64_t lcap = cap_get(Pk, d.lcap), rcap = cap_get(Pk, d.rcap);
             const int64_t l = d.l_cap ? lcap : d.l_cur ? cur : d.lc;
             const int64_t r = d.r_cap ? rcap : d.r_cur ? cur : d.rc;
-            const bool ln = d.l_null || (d.l_cur && curn) || (d.l_cap && ((P[kk].cn >> d.lcap) & 1u));
-            const bool rn = d.r_null || (d.r_cur && curn) || (d.r_cap && ((P[kk].cn >> d.rcap) & 1u));
+            const bool ln = d.l_null || (d.l_cur && curn) || (d.l_cap && ((Pk.cn >> d.lcap) & 1u));
+            const bool rn = d.r_null || (d.r_cur && curn) || (d.r_cap && ((Pk.cn >> d.rcap) & 1u));
             pass = pass && !ln && !rn && cmp_keys(d.mask, d.f64, l, r);
           }
+          return pass;
+        };
+        // R: the partial residual, once per register set that holds a candidate. The sets are walked by
+        // a run-time index over one copy of the interpreter (K inlined copies per state would not fit
+        // the registers), the set's captures picked by compares; bit kk of rfail: the lane's partial of
+        // set kk fails
+        uint32_t rfail = 0;
+        if constexpr (R) {
+          if (d.rp_e > d.rp_b && cpass) {
+            uint32_t cand = 0;
+#pragma unroll
+            for (int kk = 0; kk < K; ++kk) {
+              bool exp;
+              cand |= (atoms_pass(P[kk], exp) ? 1u : 0u) << kk;
+            }
+#pragma unroll 1
+            for (int k2 = 0; k2 < K; ++k2) {
+              if (__ballot((cand >> k2) & 1u) == 0) continue;
+              Caps C = caps_of(P[0]);
+#pragma unroll
+              for (int kk = 1; kk < K; ++kk) {
+                const Caps X = caps_of(P[kk]);
+                const bool me = k2 == kk;
+                C.c0 = me ? X.c0 : C.c0; C.c1 = me ? X.c1 : C.c1; C.c2 = me ? X.c2 : C.c2; C.c3 = me ? X.c3 : C.c3;
+                C.cn = me ? X.cn : C.cn;
+              }
+              if (!partial_residual(L.rcode, d.rp_b, d.rp_e, col_key, cnul_k, k, C)) rfail |= 1u << k2;
+            }
+          }
+        }
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) {
+          if (__ballot(P[kk].st == s) == 0) continue;
+          bool exp;
+          bool pass = atoms_pass(P[kk], exp);
+          if constexpr (R) pass = pass && !((rfail >> kk) & 1u);
           if (last) {
             const uint64_t m = __ballot(pass);
             if (m && emit_ok) {
@@ -506,7 +585,7 @@ __device__ __forceinline__ int page_store(int64_t* tab, int cap, int64_t at, int
   return __popcll(m);
 }
 
-template <int S>
+template <int S, bool R>
 __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
   static_assert(S >= 2, "a one-state chain holds no partials");
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -538,6 +617,10 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
     uint32_t cm = 0;
     for (int c = 0; c < n_cap; ++c) cm |= (Q->cap_slot[c] == s ? 1u : 0u) << c;
     d.capmask = cm;
+    if constexpr (R) {
+      d.rp_b = Q->rp_b[s];
+      d.rp_e = Q->rp_e[s];
+    }
     D[s] = d;
   }
 
@@ -619,6 +702,10 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
             xnul |= ((cnul >> col) & 1u) << s;
           }
         }
+        if constexpr (R) {
+          const int rb = Q->rt_b[s], re = Q->rt_e[s];
+          if (re > rb) ok = ok && tile_residual(L.rcode, rb, re, col_key, cnul);
+        }
       }
       smask[s] = __ballot(ok);
     }
@@ -652,6 +739,7 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
         const int64_t cseq = L.b.seq_base + j;
         const uint32_t capn_k = __builtin_amdgcn_readlane(capn, k);
         const uint32_t xnul_k = __builtin_amdgcn_readlane(xnul, k);
+        const uint32_t cnul_k = R ? __builtin_amdgcn_readlane(cnul, k) : 0u;
 #pragma unroll
         for (int s = S - 1; s >= 1; --s) {
           const StateDesc& d = D[s];
@@ -671,6 +759,15 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
             const bool ln = d.l_null || (d.l_cur && curn) || (d.l_cap && ((P.cn >> d.lcap) & 1u));
             const bool rn = d.r_null || (d.r_cur && curn) || (d.r_cap && ((P.cn >> d.rcap) & 1u));
             pass = pass && !ln && !rn && cmp_keys(d.mask, d.f64, l, r);
+          }
+          // (a lane of the fresh page that is not open yet is not in_s: it never passes)
+          if constexpr (R) {
+            // (every lane evaluates: the current event's words are read from lane k, which computes
+            // them only while it is active -- `pass && ...` would mask it off with its own partial)
+            if (d.rp_e > d.rp_b && __ballot(pass)) {
+              const bool rp = partial_residual(L.rcode, d.rp_b, d.rp_e, col_key, cnul_k, k, caps_of(P));
+              pass = pass && rp;
+            }
           }
           if (last) {
             const uint64_t m = __ballot(pass);
@@ -796,42 +893,59 @@ __global__ void chain_relayout_kernel(const int64_t* src, int64_t* dst, int64_t 
 
 }  // namespace sdh
 
-template <int S>
+template <int S, bool R>
 static hipError_t launch_s(int k, const sdh::ChainLaunch* L, int n_blocks, size_t lds, hipStream_t s) {
   switch (k) {
-    case 1: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 1>), dim3(n_blocks), dim3(256), lds, s, *L); break;
-    case 2: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 2>), dim3(n_blocks), dim3(256), lds, s, *L); break;
-    case 4: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 4>), dim3(n_blocks), dim3(256), lds, s, *L); break;
-    case 8: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 8>), dim3(n_blocks), dim3(256), lds, s, *L); break;
+    case 1: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 1, R>), dim3(n_blocks), dim3(256), lds, s, *L); break;
+    case 2: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 2, R>), dim3(n_blocks), dim3(256), lds, s, *L); break;
+    case 4: hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 4, R>), dim3(n_blocks), dim3(256), lds, s, *L); break;
+    case 8:
+      // (R = true with partials: not built, the engine pages past 256 partials -- chain_reg_limit)
+      if constexpr (R && S >= 2) return hipErrorInvalidValue;
+      else hipLaunchKernelGGL((sdh::nfa_chain_kernel<S, 8, R>), dim3(n_blocks), dim3(256), lds, s, *L);
+      break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-// host-side launchers (C linkage inside the library)
-extern "C" hipError_t sdh_launch_chain(int n_states, int k, const sdh::ChainLaunch* L, int n_blocks,
-                                       size_t lds, hipStream_t s) {
-  if (n_blocks <= 0) return hipSuccess;
+template <bool R>
+static hipError_t launch_r(int n_states, int k, const sdh::ChainLaunch* L, int n_blocks, size_t lds, hipStream_t s) {
   switch (n_states) {
-    case 1: return launch_s<1>(k, L, n_blocks, lds, s);
-    case 2: return launch_s<2>(k, L, n_blocks, lds, s);
-    case 3: return launch_s<3>(k, L, n_blocks, lds, s);
-    case 4: return launch_s<4>(k, L, n_blocks, lds, s);
+    case 1: return launch_s<1, R>(k, L, n_blocks, lds, s);
+    case 2: return launch_s<2, R>(k, L, n_blocks, lds, s);
+    case 3: return launch_s<3, R>(k, L, n_blocks, lds, s);
+    case 4: return launch_s<4, R>(k, L, n_blocks, lds, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+template <bool R>
+static hipError_t launch_paged_r(int n_states, const sdh::ChainLaunch* L, int n_blocks, hipStream_t s) {
+  switch (n_states) {
+    case 2: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<2, R>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 3: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<3, R>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 4: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<4, R>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// host-side launchers (C linkage inside the library). resid: a K_chain query of the engine has a
+// residual program (chain_pred.h), so the launch takes the R = true instantiation; one S, one K and
+// one R serve a whole launch, and an R = true kernel runs the atom-only queries beside it unchanged
+extern "C" hipError_t sdh_launch_chain(int n_states, int k, int resid, const sdh::ChainLaunch* L, int n_blocks,
+                                       size_t lds, hipStream_t s) {
+  if (n_blocks <= 0) return hipSuccess;
+  return resid ? launch_r<true>(n_states, k, L, n_blocks, lds, s) : launch_r<false>(n_states, k, L, n_blocks, lds, s);
 }
 
 // the paged form: chains of two to four states (a one-state chain holds no partials and stays on
 // sdh_launch_chain)
-extern "C" hipError_t sdh_launch_chain_paged(int n_states, const sdh::ChainLaunch* L, int n_blocks, hipStream_t s) {
+extern "C" hipError_t sdh_launch_chain_paged(int n_states, int resid, const sdh::ChainLaunch* L, int n_blocks,
+                                             hipStream_t s) {
   if (n_blocks <= 0) return hipSuccess;
-  switch (n_states) {
-    case 2: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<2>), dim3(n_blocks), dim3(256), 0, s, *L); break;
-    case 3: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<3>), dim3(n_blocks), dim3(256), 0, s, *L); break;
-    case 4: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<4>), dim3(n_blocks), dim3(256), 0, s, *L); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return resid ? launch_paged_r<true>(n_states, L, n_blocks, s) : launch_paged_r<false>(n_states, L, n_blocks, s);
 }
 
 // `rows` table rows ([q][field]) of old_cap lanes each -> new_cap lanes each (K_chain table growth)

@@ -12,6 +12,10 @@
 
 namespace sdh {
 
+namespace kg {
+struct GInsn;
+}
+
 constexpr int MAXS = 4;      // states per chain query
 constexpr int MAXCAP = 4;    // captured operand keys per partial match
 constexpr int MAXATOM = 12;  // compare atoms per query (all states)
@@ -76,6 +80,12 @@ struct ChainQuery {
   int32_t xa_col[MAXXA];       // column of its current-event operand (-1: none)
   int32_t cap_slot[MAXCAP], cap_col[MAXCAP];
   Atom atoms[MAXATOM];
+  // residual programs (chain_pred.h): per state the instructions [rt_b, rt_e) of ChainLaunch::rcode
+  // that read the current event only (tile residual: evaluated once per event, ANDed into the tile's
+  // pass mask) and [rp_b, rp_e) that read captures too (partial residual: per (partial, event)).
+  // Empty ranges for a query of atoms only, which reads none of these words
+  int32_t rt_b[MAXS], rt_e[MAXS];
+  int32_t rp_b[MAXS], rp_e[MAXS];
 };
 
 // one wave of the NFA-step launch = one (query instance, event chunk)
@@ -130,6 +140,7 @@ struct ChainLaunch {
                             //   partials per instance an overflowing item would have needed
   int64_t* scratch;         // paged form: working tables of the chunks that are not their query's
                             //   last                              [slot][NF][pcap]
+  const kg::GInsn* rcode;   // the engine's residual programs (ChainQuery::rt_* / rp_*); the R = true kernels
 };
 
 // ------------------------------------------------------------------------------------------

@@ -11,6 +11,10 @@ Nothing completes or expires a partial while A is pushed, so an A block leaves a
     python tools/chain_density.py --mode gen              the same queries with SDH_FLAG_FORCE_GEN
     python tools/chain_density.py --mode chain --push 256 --partials 512
                                                           a case that stays in the register form
+    python tools/chain_density.py --pred arith            e2=B[price > e1.price * 1.01]: a partial residual
+    python tools/chain_density.py --pred or               e2=B[price > e1.price or volume > e1.volume]
+                                                          (K_chain's general predicates; with
+                                                          --mode gen the same queries on K_gen)
 
 --root DIR imports the package (and its library) from another checkout, to compare two commits.
 ms_per_push is the median wall time of a push (it returns when its kernels have finished); live_per_query
@@ -29,6 +33,7 @@ ap.add_argument("--push", type=int, default=65536)
 ap.add_argument("--pairs", type=int, default=6, help="timed (A block, B block) pairs")
 ap.add_argument("--warmup", type=int, default=2, help="untimed pairs first (the tables grow in them)")
 ap.add_argument("--partials", type=int, default=0)
+ap.add_argument("--pred", choices=["plain", "arith", "or"], default="plain", help="e2's filter")
 ap.add_argument("--root", default=".")
 a = ap.parse_args()
 sys.path.insert(0, a.root)
@@ -43,15 +48,18 @@ from siddhi_amd.planner import plan  # noqa: E402
 from siddhi_amd.workloads import c2_threshold_text, stock_events  # noqa: E402
 
 COLS = "(symbol string, price float, volume int)"
+PRED = {"plain": "price > e1.price", "arith": "price > e1.price * 1.01",
+        "or": "price > e1.price or volume > e1.volume"}[a.pred]
 src = [f"define stream A {COLS}; define stream B {COLS};"]
 for p in range(a.patterns):
-    src.append(f"@info(name='p{p}') from every e1=A[price > {c2_threshold_text(p)}] -> e2=B[price > e1.price] "
+    src.append(f"@info(name='p{p}') from every e1=A[price > {c2_threshold_text(p)}] -> e2=B[{PRED}] "
                f"within {1 + p % 10} sec select e1.price as p1, e2.price as p2 insert into OutStream;")
 ir = plan(ql.parse(" ".join(src)))
 d = StringDictionary()
 blob = ir.serialize([d.intern(s) for s in ir.strings])
 flags = SDH_FLAG_DEVICE_MATCHES | (SDH_FLAG_FORCE_GEN if a.mode == "gen" else 0)
-out = {"mode": a.mode, "patterns": a.patterns, "push": a.push, "partials": a.partials, "root": a.root}
+out = {"mode": a.mode, "patterns": a.patterns, "push": a.push, "partials": a.partials, "pred": a.pred,
+       "root": a.root}
 try:
     eng = HipEngine(blob, stream_types=[s.attr_types for s in ir.streams], flags=flags, partials=a.partials)
     dev = torch.device("cuda:0")
