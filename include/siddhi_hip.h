@@ -197,7 +197,7 @@ typedef struct sdh_stats {
   int64_t ingest_bytes;      /* bytes copied from host batches so far                         */
   int64_t spec_kernels;      /* shape-compiled kernels this engine launches (hiprtc at create; */
                              /* SDH_SPEC=0 off, 1 every shape, default shapes of >= 128 queries) */
-  int64_t pool_regrows;      /* K_gen pool / list and K_chain table growths (each re-lays the     */
+  int64_t pool_regrows;      /* K_gen pool / list, K_chain and K_part table growths (each re-lays the */
                              /* state and re-runs the push that overflowed; the reference's lists */
                              /* are unbounded)                                                    */
   int64_t last_slab_items;   /* K_slab work items of the last push: key segments x groups         */
@@ -323,7 +323,10 @@ int sdh_engine_pending_matches(sdh_engine* e, int64_t* n);
  *    sequence of records, each identified by the low 32 bits of its first word, lo = (int32)w[0]:
  *      lo >= 0       a full record of lo words: {lo, query, key, ts, trigger seq, emission index,
  *                    S | stream << 16, then per state slot: c, c event seqs} (stream 0xFFFF: an absent
- *                    state's timer match; key -1 when unpartitioned, else the raw partition key);
+ *                    state's timer match; key -1 when unpartitioned, else the raw partition key). Bit 32
+ *                    of the S | stream word set: a partitioned chain match too old for its narrow record
+ *                    (kind 3); its emission index is unused, one event's matches of a (query, key) are
+ *                    ordered by ascending (seq of slot S-2, .., seq of slot 0) -- mask the word's fields;
  *      -lo >> 16 == 0: K_part logical (or / and) match, -lo words (4): w[0] >> 32 = query,
  *                    w[1] = {trigger batch offset (low 32), partition key id (high 32)}, then int32
  *                    distances back from the trigger (s2 - seq): e1, side A, side B (INT32_MIN: empty);
@@ -331,6 +334,11 @@ int sdh_engine_pending_matches(sdh_engine* e, int64_t* n);
  *                    the c chain events' distances (two int32 per word, low half first);
  *      -lo >> 16 == 2: K_seq window match, (-lo & 0xFFFF) words: w[0] >> 32 = query, w[1] = {trigger
  *                    batch offset, S}, then the S - 1 earlier slots' int32 distances;
+ *      -lo >> 16 == 3: K_part chain match (partitioned `every e1 -> e2 [-> e3 [-> e4]]` over one
+ *                    stream), (-lo & 0xFFFF) = 2 + S / 2 words: w[0] >> 32 = query, w[1] = {trigger batch
+ *                    offset, partition key id}, then the S - 1 earlier slots' int32 distances, slot 0
+ *                    first, two per word, an unused upper half INT32_MIN (3 words: S = 2 if w[2]'s upper
+ *                    half is INT32_MIN, else 3; 4 words: S = 4);
  *      -lo >> 16 == 4: padding of (-lo & 0xFFFF) words (skip it).
  *    A K_part record's key id is a dense id: f_query_keys[query][id] is the raw partition key (the
  *    sdh_matches.key value; f_query_keys[query] is NULL for an unpartitioned query).
@@ -478,6 +486,8 @@ int sdh_engine_gather(sdh_engine* e, int32_t device, sdh_matches* out);
 /* Diagnostic, no device needed: generate and compile (hiprtc, gfx950) the shape-compiled kernels of
  * representative K_seq / K_part shapes. Returns the number compiled, or -1 with the compiler log. */
 int sdh_spec_selftest(char* log, size_t cap);
+/* The same for K_part's chain kind: chains of 2, 3 and 4 states, with and without `within`. */
+int sdh_spec_selftest_chain(char* log, size_t cap);
 /* Test diagnostic: out[0] = the K_ratchet records the last push wrote, out[1] = an order-independent
  * hash of them (e2 seq, query, e1 seq), in either output mode (device records included). */
 int sdh_engine_debug_digest(sdh_engine* e, uint64_t* out);

@@ -155,6 +155,9 @@ void append_gen(sdh_engine* e, const int64_t* bts, int64_t seq_base, int stream)
   // records need no tiebreak pass: the matches of one (trigger event, query) come from one lane,
   // which emits them in list order, so the stable sort on the primary key keeps them in it
   if (n_wide) e->mt.n_lo = std::max(e->mt.n_lo, e->has_absent || e->has_fanout ? 3 : 1);
+  // K_part chains walk entry-major: one event's matches of an instance are ordered by the earlier
+  // slots' seqs (nfa_types.h), so their rows take the tiebreak passes
+  e->mt.n_lo = std::max(e->mt.n_lo, e->part_chain_lo);
 }
 
 void table_clear(sdh_engine* e) {
@@ -1794,7 +1797,7 @@ int sdh_engine_stats(sdh_engine* e, sdh_stats* out) {
     for (auto& ss : e->ssets) live += slab_live_partials(e, *ss);
     live += device_live_partials(e);
     e->stats.live_partials = live;
-    e->stats.pool_regrows = e->gen_regrows + e->chain_regrows;
+    e->stats.pool_regrows = e->gen_regrows + e->chain_regrows + e->part_regrows;
     e->stats.last_slab_items = e->slab_items;
     // queries per plan: K_ratchet, K_gate, K_chain, K_part, K_slab, K_seq, K_gen
     for (auto& c : e->stats.plan_queries) c = 0;

@@ -5,6 +5,7 @@
 #include "launchers.h"
 #include "chm_order.h"
 #include "java_fmt.h"
+#include "part_lower.h"
 #include "slab_lower.h"
 #include "spec.h"
 
@@ -12,87 +13,6 @@ namespace sdh {
 namespace eng {
 
 namespace {
-
-// K_part shape of a query (kpart_shape; kind < 0: none)
-struct KPart {
-  int kind = -1, sA = 1, sB = 2, cmax = 0, n_e1 = 0, n_first = 0, n_last = 0;
-};
-
-// ------------------------------------------------------------------------------------------
-// K_part shape selection (nfa_part.hip): partitioned `every e1 -> (e2 and|or e3)` and
-// `every e1 -> e2<min:max> -> e3` patterns whose structure the compact partial tables reproduce
-// exactly (the argument is in nfa_part.hip's header)
-// ------------------------------------------------------------------------------------------
-
-// every slot reference of state i's filters: (slot, chain index) pairs; false if an instruction
-// names a slot in another way than OP_ATTR / OP_STREAM_IS_NULL
-void filter_refs(const kg::LState& st, std::vector<std::pair<int64_t, int64_t>>& refs) {
-  for (const auto& f : st.filters)
-    for (const auto& in : f)
-      if (in.op == kg::OP_ATTR || in.op == kg::OP_STREAM_IS_NULL) refs.push_back({in.a, in.b});
-}
-
-KPart kpart_shape(const kg::LProgram& P, int qi, const kg::GQuery& g) {
-  KPart k;
-  const kg::LQuery& q = P.q[qi];
-  if (q.partition < 0 || q.type != kg::Q_PATTERN || q.st.size() != 3) return k;
-  for (const auto& x : q.st)
-    if (x.waiting != -1) return k;  // absent sides run on K_gen
-  // start ids exist only with `within` (StateInputStreamParser.java:126-138): then e1 alone
-  if (!(q.start_ids.empty() || (q.start_ids.size() == 1 && q.start_ids[0] == 0)) || g.max_depth > kg::RSTACK) return k;
-  if (q.start_ids.empty() && q.within >= 0) return k;
-  const int s = q.st[0].stream;
-  for (const auto& x : q.st)
-    if (x.stream != s || x.within_every != -1 || x.callback != -1) return k;
-  if (q.recvs.size() != 1 || q.recvs[0].stream != s || q.recvs[0].procs.size() != 3 || q.recvs[0].procs[0] != 0)
-    return k;
-  const kg::LState& e1 = q.st[0];
-  if (e1.kind != kg::K_STREAM || !e1.is_start || e1.next_every != 0 || e1.has_selector) return k;
-  std::vector<std::pair<int64_t, int64_t>> r;
-  const auto& procs = q.recvs[0].procs;
-  if (q.st[1].kind == kg::K_LOGICAL) {
-    const kg::LState &a = q.st[1], &b = q.st[2];
-    if (b.kind != kg::K_LOGICAL || a.partner != 2 || b.partner != 1 || a.ltype != b.ltype) return k;
-    for (const auto* x : {&a, &b})
-      if (x->is_start || x->next_pre != -1 || x->next_every != -1 || !x->has_selector) return k;
-    if (e1.next_pre != 1 && e1.next_pre != 2) return k;
-    if (!((procs[1] == 1 && procs[2] == 2) || (procs[1] == 2 && procs[2] == 1))) return k;
-    for (int i = 1; i <= 2; ++i) {  // the sides' filters read only their own slot (event-only)
-      r.clear();
-      filter_refs(q.st[i], r);
-      for (const auto& x : r)
-        if (x.first != i) return k;
-    }
-    k.sA = procs[1];  // registration order: the side processed second
-    k.sB = procs[2];
-    k.kind = a.ltype == kg::L_AND ? PK_AND : PK_OR;
-    return k;
-  }
-  const kg::LState &c = q.st[1], &e3 = q.st[2];
-  if (c.kind != kg::K_COUNT || c.min < 1 || c.max > PK_CMAX || c.min > c.max) return k;
-  if (c.next_pre != 2 || c.next_every != -1 || c.has_selector || e1.next_pre != 1) return k;
-  if (e3.kind != kg::K_STREAM || e3.next_pre != -1 || e3.next_every != -1 || !e3.has_selector) return k;
-  if (procs[1] != 1 || procs[2] != 2) return k;
-  r.clear();
-  filter_refs(c, r);  // the count filter reads only the event it is appending (CURRENT)
-  for (const auto& x : r)
-    if (x.first != 1 || x.second != -1) return k;
-  r.clear();
-  filter_refs(e3, r);  // e3 reads e1, e2[0], e2[last] (= CURRENT of another state) and itself
-  const int ncap = g.n_cap[s];
-  for (const auto& x : r) {
-    if (x.first == 1) {
-      if (x.second == 0) k.n_first = ncap;
-      else if (x.second == -1) k.n_last = ncap;
-      else return k;
-    } else if (x.first == 0) {
-      k.n_e1 = ncap;
-    }
-  }
-  k.cmax = c.max;
-  k.kind = PK_COUNT;
-  return k;
-}
 
 // Shape-compiled kernels (spec.h): SDH_SPEC=0 none, 1 every shape, "require" every shape and a
 // failed compile is an error; default: shapes that fill at least two waves (a compile costs about
@@ -235,15 +155,21 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
     e->routes[partition] = std::move(r);
   };
   auto add_part_sets = [&](int partition, const std::vector<int>& members) {
-    for (int kind = PK_OR; kind <= PK_COUNT; ++kind) {
+    // one set per (kind, stream): every state of a K_part shape reads one stream, and a set's groups
+    // share one buffer selector per key (cur / nxt), so all of them must run on the same pushes --
+    // those of their stream. (PK_CHAIN last: older apps keep their set order.)
+    const int n_streams = (int)e->prog.stream_types.size();
+    for (int kind = PK_OR; kind <= PK_CHAIN; ++kind)
+    for (int stream = 0; stream < n_streams; ++stream) {
       std::vector<int> m;
       for (int qi : members)
-        if (kpart[qi].kind == kind) m.push_back(qi);
+        if (kpart[qi].kind == kind && e->lp.q[qi].st[0].stream == stream) m.push_back(qi);
       if (m.empty()) continue;
       route_of(partition);
       auto ps = std::make_unique<sdh_engine::PartSet>();
       ps->partition = partition;
       ps->kind = kind;
+      ps->stream = stream;
       ps->group_base = (int)(e->lane_q.size() / 64);
       ps->n_groups = add_groups(m, false);
       const KPart& k0 = kpart[m[0]];
@@ -256,8 +182,11 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
         ps->n_last = std::max(ps->n_last, kpart[qi].n_last);
         if (kpart[qi].sA != ps->sA || kpart[qi].sB != ps->sB) throw Error(SDH_E_UNSUPPORTED, "K_part side order");
       }
-      ps->ew = kind == PK_COUNT ? 3 + ps->cmax + ps->n_e1 + ps->n_first + ps->n_last : 3;
+      // (a chain partial uses the count layout: cmax = S - 2 slot seqs, then slots 0, 1, 2's words)
+      const bool wide_entry = kind == PK_COUNT || kind == PK_CHAIN;
+      ps->ew = wide_entry ? 3 + ps->cmax + ps->n_e1 + ps->n_first + ps->n_last : 3;
       ps->cap = kind == PK_COUNT ? 8 : 16;
+      if (kind == PK_CHAIN) e->part_chain_lo = std::max(e->part_chain_lo, ps->cmax + 1);
       if (const char* v = sdh::knob("SDH_KPART_CAP")) ps->cap = std::max(1, atoi(v));
       e->psets.push_back(std::move(ps));
     }
@@ -919,7 +848,7 @@ void part_sets(Pass& p, int pi, const sdh_engine::Route& rt, Routed r) {
   bool sorted = false;
   for (size_t si = 0; si < e->psets.size(); ++si) {
     auto& ps = *e->psets[si];
-    if (ps.partition != pi) continue;
+    if (ps.partition != pi || ps.stream != p.stream) continue;
     part_grow(e, ps, r.n_keys);
     if (!sorted && !sdh::knob("SDH_KPART_GATHER")) {
       e->sb_buf.ensure(sdh_sorted_batch_bytes(&p.B));
@@ -943,6 +872,7 @@ void part_sets(Pass& p, int pi, const sdh_engine::Route& rt, Routed r) {
     P.n_e1 = ps.n_e1;
     P.n_first = ps.n_first;
     P.n_last = ps.n_last;
+    P.wide = sdh::knob("SDH_KPART_WIDE") ? 1 : 0;
     P.st = ps.st.p;
     P.blocks = ps.key_cap * ps.n_groups;
     P.cur = ps.cur.p;
@@ -1092,7 +1022,7 @@ void partition_pass(Pass& p, int pi) {
   }
   bool reads = gen || rt.track;  // (fan-out: every key's creation counts)
   for (auto& ps : e->psets)
-    if (ps->partition == pi) reads = true;
+    if (ps->partition == pi && ps->stream == p.stream) reads = true;
   for (auto& ss : e->ssets)
     if (ss->partition == pi && !ss->glist[p.stream].empty()) reads = true;
   if (!reads) return;
@@ -1225,6 +1155,7 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
           if (e->psets[i]->cap >= (1 << 16))
             throw Error(SDH_E_CAPACITY, "more than 65536 pending partials in one K_part instance");
           part_grow_cap(e, *e->psets[i]);
+          ++e->part_regrows;
         }
       continue;
     }

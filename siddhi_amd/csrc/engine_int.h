@@ -311,10 +311,10 @@ struct sdh_engine {
     std::map<int, Fan> fan;  // [stream] per-kid positions in that stream's junction map
   };
   std::vector<std::unique_ptr<Route>> routes;  // [partition] (null: no device set uses it)
-  // K_part (nfa_part.hip): one set per (partition, kind); state blocks (key, group) double-buffered
+  // K_part (nfa_part.hip): one set per (partition, kind, stream); state blocks (key, group) double-buffered
   // per key: cur[kid] says which of st[0] / st[1] holds the key's current tables
   struct PartSet {
-    int partition = -1, kind = 0;
+    int partition = -1, kind = 0, stream = 0;  // (the one stream every query of the set reads)
     int group_base = 0, n_groups = 0;
     int cap = 8, ew = 3, sA = 1, sB = 2, cmax = 0, n_e1 = 0, n_first = 0, n_last = 0;
     int64_t key_cap = 0;
@@ -325,6 +325,8 @@ struct sdh_engine {
     std::map<int, hipFunction_t> spec;  // shape template -> shape-compiled kernel (spec.h)
   };
   std::vector<std::unique_ptr<PartSet>> psets;
+  int64_t part_regrows = 0;          // K_part table growths so far (sdh_stats.pool_regrows)
+  int part_chain_lo = 0;            // PK_CHAIN sets: the tiebreak passes their rows need (states - 1; 0: none)
   // K_slab (nfa_slab.hip): one set per partition; its queries' partials as sparse entries, one block
   // per (key, group) in nsub sub-rings of a slab, found through the directory [key][group]
   struct SlabSet {

@@ -46,6 +46,8 @@ extern "C" hipError_t sdh_select_placed(const sdh::sel::Tables* T, const sdh::se
 
 extern "C" hipError_t sdh_launch_gen(const sdh::GenLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_part(const sdh::PartLaunch* L, hipStream_t s);
+// the interpreted kernel of K_part's chain kind (nfa_part_chain.hip; sdh_launch_part hands PK_CHAIN on)
+extern "C" hipError_t sdh_launch_part_chain(const sdh::PartLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_seq(const sdh::SeqLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_slab(const sdh::SlabLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_slab_rollback(uint64_t* dir, const uint64_t* journal, const uint64_t* journal_idx, int64_t n,

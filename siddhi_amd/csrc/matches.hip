@@ -293,6 +293,12 @@ __global__ __launch_bounds__(256) void append_chain_kernel(
 __device__ __forceinline__ int32_t lo32(int64_t w) { return (int32_t)(uint32_t)(uint64_t)w; }
 __device__ __forceinline__ int32_t hi32(int64_t w) { return (int32_t)(uint32_t)((uint64_t)w >> 32); }
 
+// the states of a narrow chain record (nfa_types.h kind 3: 2 + S / 2 words, an unused half INT32_MIN)
+__device__ __forceinline__ int nrec_chain_states(const int64_t* r) {
+  const int words = (-lo32(r[0])) & 0xFFFF;
+  return words >= 4 ? 4 : hi32(r[2]) == INT32_MIN ? 2 : 3;
+}
+
 __global__ __launch_bounds__(256) void gen_rec_words_kernel(const int64_t* __restrict__ out,
                                                             const int64_t* __restrict__ rec_off, int64_t n_rec,
                                                             int64_t* __restrict__ tw, unsigned long long* n_wide) {
@@ -311,6 +317,8 @@ __global__ __launch_bounds__(256) void gen_rec_words_kernel(const int64_t* __res
     tw[i] = 5 + hi32(r[2]);
   } else if (((-l0) >> 16) == NREC_KIND_SEQ) {    // K_seq window: (1, seq) x S
     tw[i] = 2 * hi32(r[1]);
+  } else if (((-l0) >> 16) == NREC_KIND_CHAIN) {  // K_part chain: (1, seq) x S
+    tw[i] = 2 * nrec_chain_states(r);
   } else {  // or / and: (1, e1), then per side (1, seq) or (0)
     tw[i] = 2 + (hi32(r[2]) == INT32_MIN ? 1 : 2) + (lo32(r[3]) == INT32_MIN ? 1 : 2);
   }
@@ -351,6 +359,30 @@ __global__ __launch_bounds__(256) void append_gen_kernel(const int64_t* __restri
     for (int j = 0; j < S - 1; ++j) {
       w[2 * j] = 1;
       w[2 * j + 1] = sq - (j & 1 ? hi32(r[2 + j / 2]) : lo32(r[2 + j / 2]));
+    }
+    w[2 * S - 2] = 1;
+    w[2 * S - 1] = sq;
+    T.wlen[row] = 2 * S;
+    return;
+  }
+  if (l0 < 0 && ((-l0) >> 16) == NREC_KIND_CHAIN) {  // narrow K_part chain record
+    const int q = hi32(r[0]), S = nrec_chain_states(r);
+    const int64_t off = (int64_t)(uint32_t)lo32(r[1]);
+    const uint32_t kid = (uint32_t)hi32(r[1]);
+    const int64_t sq = seq_base + off;
+    T.seq[row] = sq;
+    T.hi[row] = hi_key(sq, seq_ref, out_rank[(int64_t)q * n_streams + bstream]);
+    T.q[row] = q;
+    T.key[row] = qkeys[q][kid];
+    T.ts[row] = bts[off];
+#pragma unroll
+    for (int j = 0; j < MAXLO; ++j) {
+      const int64_t sj = j < S - 1 ? sq - (j & 1 ? hi32(r[2 + j / 2]) : lo32(r[2 + j / 2])) : 0;
+      T.lo[j][row] = (uint64_t)sj;  // slot j's seq; slot S-2 is compared first
+      if (j < S - 1) {
+        w[2 * j] = 1;
+        w[2 * j + 1] = sj;
+      }
     }
     w[2 * S - 2] = 1;
     w[2 * S - 1] = sq;
@@ -411,6 +443,12 @@ __global__ __launch_bounds__(256) void append_gen_kernel(const int64_t* __restri
     T.lo[2][row] = (uint64_t)r[5] >> 32;
     T.lo[1][row] = (uint64_t)fan_rank[(int64_t)q * n_streams + stream];
     T.lo[0][row] = (uint64_t)r[5] & 0xFFFFFFFFull;
+  } else if (r[6] & GREC_LO_SLOTS) {
+    // a K_part chain match too old for the narrow record: [(1, seq) x S], tiebreaks from the slots
+    const int S = (int)(r[6] & 0xFFFF);
+    T.hi[row] = hi_key(r[4], seq_ref, out_rank[(int64_t)q * n_streams + stream]);
+#pragma unroll
+    for (int j = 0; j < MAXLO; ++j) T.lo[j][row] = j < S - 1 ? (uint64_t)r[8 + 2 * j] : 0ull;
   } else {
     T.hi[row] = hi_key(r[4], seq_ref, out_rank[(int64_t)q * n_streams + stream]);
     T.lo[0][row] = (uint64_t)r[5];

@@ -163,7 +163,9 @@ extern "C" hipError_t sdh_launch_part(const sdh::PartLaunch* L, hipStream_t s) {
   switch (L->kind) {
     case sdh::PK_OR: hipLaunchKernelGGL(sdh::nfa_part_kernel<sdh::PK_OR>, grid, dim3(64), 0, s, *L); break;
     case sdh::PK_AND: hipLaunchKernelGGL(sdh::nfa_part_kernel<sdh::PK_AND>, grid, dim3(64), 0, s, *L); break;
-    default: hipLaunchKernelGGL(sdh::nfa_part_kernel<sdh::PK_COUNT>, grid, dim3(64), 0, s, *L);
+    case sdh::PK_COUNT: hipLaunchKernelGGL(sdh::nfa_part_kernel<sdh::PK_COUNT>, grid, dim3(64), 0, s, *L); break;
+    case sdh::PK_CHAIN: return sdh_launch_part_chain(L, s);  // (nfa_part_chain.hip)
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

@@ -401,15 +401,19 @@ struct GenLaunch {
 // K_part launch (nfa_part.hip): shape-specialised partitioned patterns on compact partial tables
 //   PK_OR / PK_AND:  every e1=S[f1] -> e2=S[f2] or|and e3=S[f3] [within T]
 //   PK_COUNT:        every e1=S[f1] -> e2=S[f2] <min:max> -> e3=S[f3(e1, e2[0], e2[last], cur)] [within T]
+//   PK_CHAIN:        every e1=S[f1] -> e2=S[f2(e1, cur)] [-> e3=S[f3] [-> e4=S[f4]]] [within T]
 // item = (segment of one key's events, group of 64 same-shape queries); state block of (key, group)
 // = [header words][cap entries x entry words], every word lane-interleaved ([word][lane], int64),
 // double-buffered across pushes so a push can be re-run exactly with a larger `cap`.
 // ------------------------------------------------------------------------------------------
-enum PartKind { PK_OR = 0, PK_AND = 1, PK_COUNT = 2 };
+enum PartKind { PK_OR = 0, PK_AND = 1, PK_COUNT = 2, PK_CHAIN = 3 };
 constexpr int PK_HDR = 2;      // header words: n entries; logical: filled prefix F | side << 32
 constexpr int PK_CMAX = 8;     // count <min:max> with max <= PK_CMAX on K_part
 // count-kind entry words: ts1, seq1, flags (len | inL3 << 8 | null bits << 16), chain[max], then
 // the captured words the e3 filter reads: e1's, the chain's first event's, its last event's
+// chain-kind entry words (the count layout with cmax = S - 2): ts1, seq1, flags (filled slots beyond e1
+// = the state the partial waits in minus 1 | null bits << 16 / 24 / 32), the seqs of slots 1 .. S-2,
+// then the captured words of slots 0, 1 and 2 where a later state's filter reads them
 
 // K_part's narrow match record (int64 words; beside K_gen-format records in the same buffer -- a
 // K_gen record's first word is its positive length, a narrow one's low half is minus its length):
@@ -421,6 +425,16 @@ constexpr int PK_CMAX = 8;     // count <min:max> with max <= PK_CMAX on K_part
 // The table append (matches.hip) restores the K_gen row: ts from the batch, the key from the
 // partition's key table, emission index = e1's seq (the pending-list order is the creation order).
 // A match whose distances do not fit int32 goes out as a K_gen record instead.
+// PK_CHAIN's narrow record (kind 3: -(words + 0x30000)), a partitioned chain match of S states:
+//   w0 = (uint32)(-(words + 0x30000)) | qid << 32
+//   w1 = (uint32)(trigger seq - the batch's seq_base) | key id << 32
+//   then the S - 1 earlier slots' int32 seq distances back from the trigger, slot 0 first, two per
+//   word, an unused upper half = INT32_MIN             -> 2 + S / 2 words (24 B at S = 2 and 3, 32 B at 4)
+// restored as [(1, seq) x S]; one event's matches of an instance are ordered by ascending
+// (seq of slot S-2, .., seq of slot 0) -- the order partials reached the last state's pending list --
+// so the row's tiebreaks are lo[k] = slot k's seq (later lo passes are more significant). A chain
+// match whose distances do not fit int32 goes out as a K_gen record whose word 6 carries
+// GREC_LO_SLOTS: the append takes the same tiebreaks from the record's slots (its idx word is unused).
 // K_seq's narrow record (kind 2 in w0's low half: -(words + 0x20000)), an unpartitioned window match:
 //   w0 = (uint32)(-(words + 0x20000)) | qid << 32
 //   w1 = (uint32)(trigger seq - the batch's seq_base) | S << 32
@@ -429,9 +443,11 @@ constexpr int PK_CMAX = 8;     // count <min:max> with max <= PK_CMAX on K_part
 // restored as [(1, seq) x S] with key -1, ts from the batch, emission index 0 (one match per event
 // and query).
 constexpr int NREC_ORAND_WORDS = 4;
-constexpr int NREC_KIND_COUNT = 1, NREC_KIND_SEQ = 2;
+constexpr int NREC_KIND_COUNT = 1, NREC_KIND_SEQ = 2, NREC_KIND_CHAIN = 3;
+constexpr int64_t GREC_LO_SLOTS = 1ll << 32;  // K_gen record word 6 (S | stream << 16): tiebreaks from the slots
 __host__ __device__ inline int nrec_count_words(int c) { return 3 + (c + 1) / 2; }
 __host__ __device__ inline int nrec_seq_words(int S) { return 2 + S / 2; }
+__host__ __device__ inline int nrec_chain_words(int S) { return 2 + S / 2; }
 constexpr int NREC_MIN_WORDS = 3;  // (K_seq's at S <= 3; record-offset capacities are words / 3)
 __host__ __device__ inline int64_t nrec_pack(int64_t lo, int64_t hi) {
   return (int64_t)(((uint64_t)(uint32_t)(int32_t)lo) | ((uint64_t)(uint32_t)(int32_t)hi << 32));
@@ -450,6 +466,7 @@ struct PartLaunch {
   int32_t sA, sB;             // logical: state ids of the side processed second (A) and first (B)
   int32_t cmax;               // count: chain words per entry (the set's largest max)
   int32_t n_e1, n_first, n_last;  // count: captured words stored per entry (0 or the stream's n_cap)
+                              // (chain: cmax = S - 2 slot seqs; the words of slots 0, 1 and 2)
   int32_t n_items;            // key segments x gn
   int64_t* st;                // [buffer 0/1][block][PK_HDR + cap * ew][64], block = kid * groups + g
   int64_t blocks;             // blocks per buffer
@@ -461,6 +478,7 @@ struct PartLaunch {
                               // gives each position's batch index (its seq)
   int32_t* err;               // [0] entry capacity, [2] output overflow
   unsigned long long* prof;   // SDH_PART_PROF builds: per-phase clock sums (part_body.h), else null
+  int32_t wide;               // chain: every match as a K_gen record (SDH_KPART_WIDE, the >int32 path)
 };
 
 // ------------------------------------------------------------------------------------------

@@ -2,10 +2,12 @@
 // family); the kernel body, instantiated by nfa_part.hip with the interpreted filters
 // (PartInterp) and by spec.hip with a shape's filters compiled to straight-line code.
 //
-// Shapes (kpart_shape in engine_gen.hip decides; every filter in the IR's typed bytecode):
+// Shapes (kpart_shape in part_lower.h decides; every filter in the IR's typed bytecode):
 //   PK_OR / PK_AND  every e1=S[f1] -> e2=S[f2] or|and e3=S[f3] [within T]     (f1, f2, f3 event-only)
 //   PK_COUNT        every e1=S[f1] -> e2=S[f2] <min:max> -> e3=S[f3] [within T]
 //                   (f1, f2 event-only; f3 may read e1, e2[0], e2[last] and the current event)
+//   PK_CHAIN        every e1=S[f1] -> e2=S[f2] [-> e3=S[f3] [-> e4=S[f4]]] [within T]
+//                   (f_s may read the current event and the earlier slots; part_chain.h has its argument)
 //
 // Why compact tables are exact -- the reference's object graph for these shapes reduces to one list
 // of partials in creation order (paths relative to core/query/input/stream/state/):
@@ -37,6 +39,7 @@
 // an entry-capacity overflow re-runs the push exactly with a larger table.
 #pragma once
 #include "dev_common.h"
+#include "part_chain.h"  // PartOffs, PartEnt; the chain kind's step
 
 namespace sdh {
 
@@ -46,15 +49,6 @@ struct PartEv {
   uint32_t nul;
   __device__ int64_t word(int j) const { return w[j * 64]; }
   __device__ bool null(int j) const { return (nul >> j) & 1u; }
-};
-
-// entry word offsets of a count partial: chain words 3 .. 3+cmax-1, then e1's, the chain's first
-// and its last event's captured words (those f3 reads)
-struct PartOffs {
-  int cmax, n_e1, n_first, n_last;
-  __device__ int o_e1() const { return 3 + cmax; }
-  __device__ int o_first() const { return 3 + cmax + n_e1; }
-  __device__ int o_last() const { return 3 + cmax + n_e1 + n_first; }
 };
 
 // A partial's words wherever they live: GRef in the lane's global state block (stride 64 words),
@@ -81,26 +75,6 @@ struct RRef {
     for (int x = 0; x < EW; ++x) p[x] = (w == x) ? v : p[x];
   }
 };
-
-// a count partial as f3 sees it: e1's words, the chain's first and last event words and their null
-// bits in the flags word (16 / 24 / 32 + j)
-template <class Ref>
-struct PartEnt {
-  Ref e;
-  int64_t fl;
-  PartOffs of;
-  __device__ int64_t e1(int j) const { return e.get(of.o_e1() + j); }
-  __device__ int64_t first(int j) const { return e.get(of.o_first() + j); }
-  __device__ int64_t last(int j) const { return e.get(of.o_last() + j); }
-  __device__ bool e1_null(int j) const { return (fl >> (16 + j)) & 1; }
-  __device__ bool first_null(int j) const { return (fl >> (24 + j)) & 1; }
-  __device__ bool last_null(int j) const { return (fl >> (32 + j)) & 1; }
-};
-
-template <class Ref>
-__device__ __forceinline__ PartEnt<Ref> part_ent(const Ref& e, int64_t fl, const PartOffs& of) {
-  return PartEnt<Ref>{e, fl, of};
-}
 
 // The lane's partial table: entries 0 .. RC-1 in registers (RC = 0: none), the rest in its global
 // state block; every walk visits the entries in list (creation) order
@@ -248,7 +222,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
   tab.ew = ew;
   int n = (int)in[0];
   const int64_t hdr1 = in[64];
-  if constexpr (KIND != PK_COUNT) {  // (the count tables are read entry by entry, count_tile below)
+  if constexpr (KIND != PK_COUNT && KIND != PK_CHAIN) {  // (the count / chain tables are read entry by entry, below)
     const GRef src{const_cast<int64_t*>(in) + PK_HDR * 64};
     for (int kk = 0; kk < n; ++kk) {
       const GRef e{src.p + (int64_t)kk * ew * 64};
@@ -432,6 +406,135 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
     n = wpos;
   };
 
+  // ---- PK_CHAIN, entry-major as count_tile: each partial is loaded once per event tile, stepped
+  // through the tile's events (part_chain.h chain_step: expiry, then the filter of the state it waits
+  // in) and stored once, compacted in creation order; the partials the tile's events open follow.
+  // The exactness argument and the order of one event's matches are in part_chain.h.
+  auto chain_tile = [&](int cnt, bool first_tile) {
+    if constexpr (KIND == PK_CHAIN) {
+      // the hot words in registers (shape-compiled kernels), or in the entry's global slot (the
+      // interpreter: GMAXNA-wide rows in registers spill -- 256 VGPRs and 232 B of scratch)
+      constexpr int HMAX = Spec::kHotRegs ? 3 + 3 * Spec::kNA : 0;
+      const int S = q->n_states;  // wave-uniform (the group's shape)
+      // the set's layout holds its widest shape's captured words; this shape keeps its own, so the hot
+      // words fit the registers of a kernel compiled for this shape (the entry stride stays the set's)
+      const PartOffs so = Spec::offs(L);
+      const PartOffs of{so.cmax, min(so.n_e1, ncap), min(so.n_first, ncap), min(so.n_last, ncap)};
+      const int nh = 3 + of.n_e1 + of.n_first + of.n_last;
+      auto hot_word = [&](int x) { return x < 3 ? x : of.o_e1() + x - 3; };
+      uint64_t m1 = 0;  // the tile's events passing f1 (this lane's query)
+      if (live)
+        for (int te = 0; te < cnt; ++te) {
+          const PartEv ev{&t_w[0][te], t_nul[te]};
+          if (Spec::f1(k, q, ql, L, ev)) m1 |= 1ull << te;
+        }
+      int wmax = n;
+      for (int o2 = 32; o2 > 0; o2 >>= 1) wmax = max(wmax, __shfl_xor(wmax, o2));
+      const int64_t* __restrict__ src = (first_tile ? in : st) + PK_HDR * 64;
+      int64_t* __restrict__ dst = st + PK_HDR * 64;
+      int wpos = 0;  // entries kept so far: slots 0 .. wpos-1 of dst
+      // one partial per lane and call, as count_tile's run: the entry kk held before the tile
+      // (kk >= 0) or the one event tc opens (kk < 0)
+      auto run = [&](bool has, int kk, int tc) {
+        if (has && wpos >= L.cap) {  // no slot for it: the push re-runs exactly with a larger table
+          cap_over = true;
+          has = false;
+        }
+        int64_t h[HMAX > 0 ? HMAX : 1];
+#pragma unroll
+        for (int x = 0; x < (HMAX > 0 ? HMAX : 1); ++x) h[x] = 0;
+        int64_t* gd = dst + (int64_t)wpos * ew * 64;  // the partial's slot if it survives the tile
+        const HotRef<HMAX> e{h, gd, of.o_e1()};
+        int te0 = cnt, filled = 0;
+        int64_t fl = 0;
+        if (has && kk < 0) {  // opened by event tc: in e2's list from the next event on
+          const PartEv ev{&t_w[0][tc], t_nul[tc]};
+          fl = chain_open(e, of, ncap, t_ts[tc], t_seq[tc], ev);
+          te0 = tc + 1;
+        } else if (has) {
+          const int64_t* gs = src + (int64_t)kk * ew * 64;
+          if constexpr (HMAX > 0) {
+#pragma unroll
+            for (int x = 0; x < HMAX; ++x)
+              if (x < nh) h[x] = gs[(int64_t)hot_word(x) * 64];
+          } else if (gs != gd) {
+            for (int x = 0; x < nh; ++x) gd[(int64_t)hot_word(x) * 64] = gs[(int64_t)hot_word(x) * 64];
+          }
+          fl = e.get(2);
+          filled = (int)(fl & 0xff);
+          if (gs != gd)
+            for (int c = 0; c < filled; ++c) gd[(int64_t)(3 + c) * 64] = gs[(int64_t)(3 + c) * 64];
+          te0 = live ? 0 : cnt;
+        }
+        bool alive = has && te0 < cnt;
+        int done = -1;  // the event the partial completes on
+        const int64_t ts1 = has ? e.get(0) : 0;  // (a lane without a partial has no slot: wpos may be cap)
+        // (wave-uniform bounds: from the earliest first event of the wave's partials, until none lives)
+        int tstart = alive ? te0 : cnt;
+        for (int o2 = 32; o2 > 0; o2 >>= 1) tstart = min(tstart, __shfl_xor(tstart, o2));
+        for (int te = tstart; te < cnt; ++te) {
+          if (!__ballot(alive)) break;
+          if (!alive || te < te0) continue;
+          const PartEv ev{&t_w[0][te], t_nul[te]};
+          const int r = chain_step(S, filled, ts1, t_ts[te], within,
+                                   [&](int s) { return Spec::fs(k, q, ql, L, s, ev, part_ent(e, fl, of)); });
+          if (r == CS_ADVANCE) {
+            ++filled;
+            fl = chain_advance(e, fl, of, ncap, filled, t_seq[te], ev);
+          } else if (r != CS_WAIT) {
+            if (r == CS_DONE) done = te;
+            alive = false;
+          }
+        }
+        if (done >= 0) ++nrec;
+        if (L.sink.write_records && __ballot(done >= 0)) {
+          // the narrow record (nfa_types.h, kind 3) when e1's distance fits int32, else the K_gen
+          // record [words, qid, key, ts, seq, idx, S | stream | GREC_LO_SLOTS, (1, seq) x S]
+          const int64_t sq = done >= 0 ? t_seq[done] : 0;
+          const int64_t e1s = done >= 0 ? e.get(1) : 0;  // (only a lane with a match has a slot to read)
+          const bool nar = nb_ok && !L.wide && sq - e1s <= (int64_t)INT32_MAX;
+          const int words = nar ? nrec_chain_words(S) : 7 + 2 * S;
+          o.emit_n(done >= 0 ? 1 : 0, words, [&](auto r) {
+            if (nar) {
+              r[0] = nrec_pack(-(words + (NREC_KIND_CHAIN << 16)), qid);
+              r[1] = nrec_pack(sq - L.b.seq_base, (int64_t)kid);
+              for (int c = 0; c < S - 1; c += 2)
+                r[2 + c / 2] = nrec_pack(sq - chain_slot_seq(e, c),
+                                         c + 1 < S - 1 ? sq - chain_slot_seq(e, c + 1) : (int64_t)INT32_MIN);
+              return;
+            }
+            r[0] = words;
+            r[1] = qid;
+            r[2] = key;
+            r[3] = t_ts[done];
+            r[4] = sq;
+            r[5] = 0;  // (the tiebreaks come from the slots)
+            r[6] = (int64_t)(S | (stream << 16)) | GREC_LO_SLOTS;
+            for (int c = 0; c < S; ++c) {
+              r[7 + 2 * c] = 1;
+              r[8 + 2 * c] = c < S - 1 ? chain_slot_seq(e, c) : sq;
+            }
+          });
+        }
+        // kept: alive at the tile's end, or not run at all (opened by the tile's last event, or a
+        // lane without a query)
+        if (has && (alive || (done < 0 && te0 >= cnt))) {
+          e.set(2, (fl & ~0xffll) | (int64_t)filled);
+          if constexpr (HMAX > 0) {
+#pragma unroll
+            for (int x = 0; x < HMAX; ++x)
+              if (x < nh) gd[(int64_t)hot_word(x) * 64] = h[x];
+          }
+          ++wpos;
+        }
+      };
+      for (int kk = 0; kk < wmax; ++kk) run(kk < n, kk, 0);
+      for (int tc = 0; tc < cnt; ++tc)
+        if (__ballot((m1 >> tc) & 1)) run((m1 >> tc) & 1, -1, tc);
+      n = wpos;
+    }
+  };
+
   PPROF_T(c_setup);
   PPROF_ADD(0, c_setup - c_start);
   for (int64_t t0 = e0; t0 < e1; t0 += 64) {
@@ -455,6 +558,8 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
     PPROF_ADD(1, c_t1 - c_t0);
     if constexpr (KIND == PK_COUNT) {
       count_tile(cnt, t0 == e0);
+    } else if constexpr (KIND == PK_CHAIN) {
+      chain_tile(cnt, t0 == e0);
     } else {
     for (int te = 0; te < cnt && live; ++te) {
       const int64_t seq = t_seq[te];
@@ -592,7 +697,7 @@ __device__ __forceinline__ void part_body(const PartLaunch& L) {
   }
   PPROF_T(c_loop);
   // register entries back to the output block
-  if constexpr (RC > 0 && KIND != PK_COUNT) {
+  if constexpr (RC > 0 && KIND != PK_COUNT && KIND != PK_CHAIN) {
 #pragma unroll
     for (int kk = 0; kk < RC; ++kk)
       if (kk < n)

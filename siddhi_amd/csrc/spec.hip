@@ -245,15 +245,16 @@ std::string part_source(const kg::GQuery& g, const PartLayout& lay) {
     }
     return body + "    return ok;\n  }\n";
   };
-  const bool logical = lay.kind != PK_COUNT;
+  const bool chain = lay.kind == PK_CHAIN;
+  const bool logical = lay.kind != PK_COUNT && !chain;
   std::string fns = ev_fn("f1", 0);
   fns += ev_fn("fa", logical ? lay.sA : -1);
   fns += ev_fn("fb", logical ? lay.sB : -1);
-  fns += ev_fn("f2", logical ? -1 : 1);
+  fns += ev_fn("f2", logical || chain ? -1 : 1);
   fns += "  template <class En>\n  __device__ static bool f3(const K& k, const sdh::kg::GQuery*, const sdh::kg::GQuery*, "
          "const sdh::PartLaunch&, const sdh::PartEv& ev, const En& en) {\n    (void)k;\n    (void)ev;\n    (void)en;\n"
          "    bool ok = true;\n";
-  if (!logical) {
+  if (!logical && !chain) {
     const kg::GState& st = g.st[2];
     for (int f = 0; f < st.n_filt; ++f) {
       const std::string r = emit_filter(
@@ -275,6 +276,33 @@ std::string part_source(const kg::GQuery& g, const PartLayout& lay) {
     fns += "    ok = false;\n";
   }
   fns += "    return ok;\n  }\n";
+  if (chain) {
+    // state s of a chain: slot s is the event, slots 0 / 1 / 2 below it the partial's e1 / first /
+    // last words (the interpreted form is part_chain.h chain_filter); fs picks the state's function
+    for (int sid = 1; sid < g.n_states; ++sid) {
+      fns += fmt("  template <class En>\n  __device__ static bool fc%d(const K& k, const sdh::PartEv& ev, const En& en) {\n"
+                 "    (void)k;\n    (void)ev;\n    (void)en;\n    bool ok = true;\n", sid);
+      const kg::GState& st = g.st[sid];
+      for (int f = 0; f < st.n_filt; ++f) {
+        const std::string r = emit_filter(
+            g, st.fb[f], st.fe[f], fmt("c%df%d_", sid, f), K,
+            [&](const kg::GInsn& in) {
+              const int j = (int)in.imm;
+              if (in.a > sid || in.a < 0 || !here(in)) return fmt("sdh::kg::Val{%d, 1, 0}", in.res);
+              if (in.a == sid) return fmt("sdh::kg::sp_attr<%d>(ev.word(%d), ev.null(%d))", in.res, j, j);
+              const char* which = in.a == 0 ? "e1" : in.a == 1 ? "first" : "last";
+              return fmt("sdh::kg::sp_attr<%d>(en.%s(%d), en.%s_null(%d))", in.res, which, j, which, j);
+            },
+            [&](const kg::GInsn& in) { return std::string(in.a >= 0 && in.a <= sid && here(in) ? "false" : "true"); }, fns);
+        fns += "    ok = ok & sdh::kg::sp_true(" + r + ");\n";
+      }
+      fns += "    return ok;\n  }\n";
+    }
+    fns += "  template <class En>\n  __device__ static bool fs(const K& k, const sdh::kg::GQuery*, const sdh::kg::GQuery*, "
+           "const sdh::PartLaunch&, int s, const sdh::PartEv& ev, const En& en) {\n";
+    for (int sid = g.n_states - 1; sid >= 2; --sid) fns += fmt("    if (s == %d) return fc%d(k, ev, en);\n", sid, sid);
+    fns += "    return fc1(k, ev, en);\n  }\n";
+  }
   std::string s = tuning_defines() + header() + "#include \"part_body.h\"\n\nstruct SpecPart {\n";
   int na = 1;  // captured words the tile staging holds
   for (int st = 0; st < kg::GMAXSTREAM; ++st) na = std::max(na, (int)g.n_cap[st]);
@@ -393,5 +421,52 @@ extern "C" int sdh_spec_selftest(char* log, size_t cap) {
     }
     ++ok;
   }
+  return ok;
+}
+
+// The same check for K_part's chain kind (PK_CHAIN): filterless chains of 2, 3 and 4 states, with and
+// without `within`. Returns the number compiled, or -1 with the first log in `log`.
+extern "C" int sdh_spec_selftest_chain(char* log, size_t cap) {
+  using namespace sdh;
+  int ok = 0;
+  for (int S = 2; S <= 4; ++S)
+    for (int64_t within : {(int64_t)-1, (int64_t)10}) {
+      // f1 = a0 > const; f_s = a0 > e_{s-1}.a0 and, from e3 on, not (e1.a0 is null): every state's filter
+      // reads an earlier slot, so the e1 / first / last accessors and fs's dispatch are compiled
+      kg::GQuery g{};
+      g.n_states = S;
+      g.within = within;
+      g.n_cap[0] = 1;
+      g.cap_type[0][0] = kg::T_FLOAT;
+      int pc = 0;
+      auto put = [&](int op, int lt, int rt, int res, int a, int64_t b, int64_t imm) {
+        g.code[pc++] = kg::GInsn{(int8_t)op, (int8_t)lt, (int8_t)rt, (int8_t)res, a, b, imm};
+      };
+      for (int s = 0; s < S; ++s) {
+        kg::GState& st = g.st[s];
+        st.kind = kg::K_STREAM;
+        st.n_filt = 1;
+        st.fb[0] = pc;
+        put(kg::OP_ATTR, 0, 0, kg::T_FLOAT, s, -1, 0);
+        if (s == 0) put(kg::OP_CONST, 0, 0, kg::T_FLOAT, 0, 0, 0x41a00000);  // 20.0f
+        else put(kg::OP_ATTR, 0, 0, kg::T_FLOAT, s - 1, 0, 0);
+        put(kg::OP_CMP, kg::T_FLOAT, kg::T_FLOAT, kg::T_BOOL, 0, 0, kg::CMP_GT);
+        if (s >= 2) {
+          put(kg::OP_ATTR, 0, 0, kg::T_FLOAT, 0, 0, 0);
+          put(kg::OP_IS_NULL, 0, 0, kg::T_BOOL, 0, 0, 0);
+          put(kg::OP_NOT, 0, 0, kg::T_BOOL, 0, 0, 0);
+          put(kg::OP_AND, 0, 0, kg::T_BOOL, 0, 0, 0);
+        }
+        st.fe[0] = pc;
+      }
+      g.n_code = pc;
+      const spec::PartLayout lay{PK_CHAIN, 1, 2, S - 2, 1, S > 2 ? 1 : 0, S > 3 ? 1 : 0, 3 + (S - 2) + (S - 1), 0};
+      std::string err;
+      if (spec::compile(spec::part_source(g, lay), "gfx950", &err).empty()) {
+        if (log && cap) snprintf(log, cap, "%s", err.c_str());
+        return -1;
+      }
+      ++ok;
+    }
   return ok;
 }

@@ -88,6 +88,18 @@ def c2_app(n_patterns: int, within=None, first: int = 0, step: int = 1) -> str:
     return " ".join(qs)
 
 
+def c2p_app(n_patterns: int, within=None, first: int = 0, step: int = 1) -> str:
+    """The C2 family's thresholds and windows per symbol: the same queries inside `partition with
+    (symbol of StockStream)` (K_part's chain kind; tools/part_chain_bench.py)."""
+    qs = []
+    for p in range(first, first + n_patterns * step, step):
+        w = c2_within_sec(p) if within is None else within
+        qs.append(f"@info(name='p{p}') from every e1=StockStream[price > {c2_threshold_text(p)}] -> "
+                  f"e2=StockStream[price > e1.price] within {w} sec "
+                  f"select e1.price as p1, e2.price as p2 insert into OutStream;")
+    return f"{STOCK_STREAM} partition with (symbol of StockStream) begin {' '.join(qs)} end;"
+
+
 def c2x_volume(p: int) -> int:
     return 200 + (p % 7) * 100
 
