@@ -189,7 +189,8 @@ typedef struct sdh_stats {
   double last_kernel_ms;     /* device time of the last NFA-step launch (HIP events)         */
   double last_kernel_bytes;  /* algorithmic bytes of that launch (DESIGN.md roofline model)   */
   int64_t last_gen_items;    /* K_gen work items (waves) of the last push: groups x key       */
-                             /* segments, or groups x event chunks           */
+                             /* segments, or groups x event chunks; plus     */
+                             /* K_wave's, one wave per query (§3.13)                          */
   int64_t last_seq_items;    /* K_seq work items of the last push: groups x window chunks     */
   int64_t last_part_items;   /* K_part work items of the last push: groups x key segments     */
   double last_ingest_ms;     /* host-to-HBM copy time of the last host-resident batch (side   */
@@ -197,7 +198,7 @@ typedef struct sdh_stats {
   int64_t ingest_bytes;      /* bytes copied from host batches so far                         */
   int64_t spec_kernels;      /* shape-compiled kernels this engine launches (hiprtc at create; */
                              /* SDH_SPEC=0 off, 1 every shape, default shapes of >= 128 queries) */
-  int64_t pool_regrows;      /* K_gen pool / list, K_chain and K_part table growths (each re-lays the */
+  int64_t pool_regrows;      /* K_gen pool / list, K_chain, K_part and K_wave table growths (each re-lays the */
                              /* state and re-runs the push that overflowed; the reference's lists */
                              /* are unbounded)                                                    */
   int64_t last_slab_items;   /* K_slab work items of the last push: key segments x groups         */
@@ -205,7 +206,8 @@ typedef struct sdh_stats {
                              /* rows (no sort at poll; matches.hip ratchet_place_kernel)          */
   int64_t plan_queries[8];   /* queries (pattern instances of this shard) per device plan:         */
                              /* [0] K_ratchet [1] K_gate [2] K_chain [3] K_part [4] K_slab         */
-                             /* [5] K_seq [6] K_gen. [2] counts the chains with    */
+                             /* [5] K_seq [6] K_gen [7] K_wave (unpartitioned count patterns, a   */
+                             /* wave per query). [2] counts the chains with         */
                              /* or / not / is null / arithmetic filters too (residual programs)   */
 } sdh_stats;
 

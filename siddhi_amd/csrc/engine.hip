@@ -122,6 +122,10 @@ void upload_qkeys(sdh_engine* e) {
     if (g.partition >= 0 && g.partition < (int)e->routes.size() && e->routes[g.partition] && g.qid >= 0 &&
         (size_t)g.qid < nq)
       qk[(size_t)g.qid] = e->routes[g.partition]->key_of_id.p;
+  // K_wave's narrow records carry key id 0 of a one-word table holding -1 (an unpartitioned query's key)
+  for (const auto& ws : e->wsets)
+    for (int gx : ws->qs)
+      if (e->gq[gx].qid >= 0 && (size_t)e->gq[gx].qid < nq) qk[(size_t)e->gq[gx].qid] = e->d_wave_key.p;
   e->d_qkeys.ensure(nq);
   HIPCHK(hipMemcpyAsync(e->d_qkeys.p, qk.data(), nq * sizeof(void*), hipMemcpyHostToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -158,6 +162,9 @@ void append_gen(sdh_engine* e, const int64_t* bts, int64_t seq_base, int stream)
   // K_part chains walk entry-major: one event's matches of an instance are ordered by the earlier
   // slots' seqs (nfa_types.h), so their rows take the tiebreak passes
   e->mt.n_lo = std::max(e->mt.n_lo, e->part_chain_lo);
+  // K_wave: one event's matches of a query come from many lanes and pages; their rows carry e1's seq
+  // as the first tiebreak (the pending-list order, nfa_wave.hip), so the poll takes that pass
+  if (!e->wsets.empty()) e->mt.n_lo = std::max(e->mt.n_lo, 1);
 }
 
 void table_clear(sdh_engine* e) {
@@ -1796,10 +1803,11 @@ int sdh_engine_stats(sdh_engine* e, sdh_stats* out) {
     }
     for (auto& ss : e->ssets) live += slab_live_partials(e, *ss);
     live += device_live_partials(e);
+    live += wave_live_partials(e);
     e->stats.live_partials = live;
-    e->stats.pool_regrows = e->gen_regrows + e->chain_regrows + e->part_regrows;
+    e->stats.pool_regrows = e->gen_regrows + e->chain_regrows + e->part_regrows + e->wave_regrows;
     e->stats.last_slab_items = e->slab_items;
-    // queries per plan: K_ratchet, K_gate, K_chain, K_part, K_slab, K_seq, K_gen
+    // queries per plan: K_ratchet, K_gate, K_chain, K_part, K_slab, K_seq, K_gen, K_wave
     for (auto& c : e->stats.plan_queries) c = 0;
     for (const auto& g : e->rg) e->stats.plan_queries[g.n_g ? 1 : 0] += g.n_lanes;
     e->stats.plan_queries[2] = (int64_t)e->lq.size();
@@ -1815,6 +1823,7 @@ int sdh_engine_stats(sdh_engine* e, sdh_stats* out) {
     for (const auto& gs : e->gsets)
       for (int g = gs->group_base; g < gs->group_base + gs->n_groups; ++g)
         e->stats.plan_queries[(size_t)g < e->group_seq.size() && e->group_seq[g] > 0 ? 5 : 6] += lanes(g);
+    for (const auto& ws : e->wsets) e->stats.plan_queries[7] += (int64_t)ws->qs.size();
     *out = e->stats;
     return SDH_OK;
   });

@@ -1,4 +1,4 @@
-// engine_gen.hip -- host side of the K_gen family (K_gen, K_seq, K_part, K_slab): lowering into sets
+// engine_gen.hip -- host side of the K_gen family (K_gen, K_seq, K_part, K_slab, K_wave): lowering into sets
 // and groups, instance arenas and their growth, the journal of exact re-runs, partition routing, and
 // the launches of one push (launch_gen -> gen_pass).
 #include "engine_int.h"
@@ -8,6 +8,7 @@
 #include "part_lower.h"
 #include "slab_lower.h"
 #include "spec.h"
+#include "wave_lower.h"
 
 namespace sdh {
 namespace eng {
@@ -79,6 +80,8 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
   std::vector<char> is_slab(e->lp.q.size(), 0);
   const bool use_part = !(e->cfg.flags & SDH_FLAG_FORCE_GEN) && !sdh::knob("SDH_NO_KPART");
   const bool use_slab = !(e->cfg.flags & SDH_FLAG_FORCE_GEN) && !sdh::knob("SDH_NO_KSLAB");
+  const bool use_wave = !(e->cfg.flags & SDH_FLAG_FORCE_GEN) && !sdh::knob("SDH_NO_KWAVE");
+  std::vector<KPart> kwave(e->lp.q.size());
   for (int qi : qis) {
     try {
       kg::GQuery g = kg::lower_gen(e->lp, qi, sz);
@@ -89,13 +92,14 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
       const bool fan = kg::reads_fanout(e->lp, qi);  // fan-out streams run on K_gen (the sweep)
       e->has_fanout |= fan;
       if (use_part && !fan) kpart[qi] = kpart_shape(e->lp, qi, g);
-      if (use_slab && !fan && kpart[qi].kind < 0) {
+      if (use_wave && !fan) kwave[qi] = wave_shape(e->lp, qi, g);  // (unpartitioned: never a K_part shape)
+      if (use_slab && !fan && kpart[qi].kind < 0 && kwave[qi].kind < 0) {
         slab::Shape sh;
         is_slab[qi] = slab::shape_of_query(e->lp, qi, g, &sh, nullptr) ? 1 : 0;
       }
-      e->gq_arena.push_back(kpart[qi].kind < 0 && !is_slab[qi]);
+      e->gq_arena.push_back(kpart[qi].kind < 0 && !is_slab[qi] && kwave[qi].kind < 0);
       e->has_absent |= g.lay.TQ > 0;
-      if (kpart[qi].kind >= 0 || is_slab[qi]) continue;  // K_part / K_slab: no K_gen arena
+      if (kpart[qi].kind >= 0 || is_slab[qi] || kwave[qi].kind >= 0) continue;  // K_part / K_slab / K_wave: no K_gen arena
       e->gB32 = std::max(e->gB32, g.lay.n32);
       e->gB64 = std::max(e->gB64, g.lay.n64);
       e->gHotS = std::max(e->gHotS, g.lay.S);
@@ -241,12 +245,44 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
     slab_init(e, *ss, sub);
     e->ssets.push_back(std::move(ss));
   };
+  // K_wave: the unpartitioned count patterns, one set per stream (a set's tables swap together, so all
+  // of its queries must run on the same pushes -- those of their stream). The entry layout is the set's
+  // widest; a table starts at one page (SDH_KWAVE_CAP: another start, for tests) and grows on overflow
+  auto add_wave_sets = [&](const std::vector<int>& members) {
+    const int n_streams = (int)e->prog.stream_types.size();
+    for (int stream = 0; stream < n_streams; ++stream) {
+      auto ws = std::make_unique<sdh_engine::WaveSet>();
+      ws->stream = stream;
+      for (int qi : members) {
+        if (kwave[qi].kind < 0 || e->lp.q[qi].st[0].stream != stream) continue;
+        ws->qs.push_back(gidx[qi]);
+        ws->cmax = std::max(ws->cmax, kwave[qi].cmax);
+        ws->n_e1 = std::max(ws->n_e1, kwave[qi].n_e1);
+        ws->n_first = std::max(ws->n_first, kwave[qi].n_first);
+        ws->n_last = std::max(ws->n_last, kwave[qi].n_last);
+        ws->na = std::max<int>(ws->na, e->gq[gidx[qi]].n_cap[stream]);
+      }
+      if (ws->qs.empty()) continue;
+      if (ws->na > kg::GMAXNA) throw Error(SDH_E_UNSUPPORTED, "K_wave: more captured attributes than GMAXNA");
+      ws->ew = 3 + ws->cmax + ws->n_e1 + ws->n_first + ws->n_last;
+      if (const char* v = sdh::knob("SDH_KWAVE_CAP")) ws->cap = std::max(64, (atoi(v) + 63) / 64 * 64);
+      ws->d_qs.ensure(ws->qs.size());
+      HIPCHK(hipMemcpy(ws->d_qs.p, ws->qs.data(), ws->qs.size() * 4, hipMemcpyHostToDevice));
+      const size_t words = ws->qs.size() * (size_t)ws->stride();
+      for (auto& b : ws->st) {
+        b.ensure(words);
+        HIPCHK(hipMemset(b.p, 0, words * 8));
+      }
+      e->wsets.push_back(std::move(ws));
+    }
+  };
   // sets: the unpartitioned queries, then one per partition; 64 queries per group (wave)
   auto add_set = [&](int partition, const std::vector<int>& members) {
     if (members.empty()) return;
     std::vector<int> gen_m;
     for (int qi : members)
-      if (kpart[qi].kind < 0 && !is_slab[qi]) gen_m.push_back(qi);
+      if (kpart[qi].kind < 0 && !is_slab[qi] && kwave[qi].kind < 0) gen_m.push_back(qi);
+    if (partition < 0) add_wave_sets(members);
     if (partition >= 0) add_part_sets(partition, members);
     if (partition >= 0) add_slab_set(partition, members);
     if (gen_m.empty()) return;
@@ -329,6 +365,13 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
   e->g_nrec.ensure(1);
   e->d_perr.ensure(std::max<size_t>(1, e->psets.size()) * 4);
   e->d_serr.ensure(std::max<size_t>(1, e->ssets.size()) * 4);
+  e->d_werr.ensure(std::max<size_t>(1, e->wsets.size()) * 4);
+  if (!e->wsets.empty()) {
+    e->d_wave_live.ensure(1);
+    const int64_t none = -1;
+    e->d_wave_key.ensure(1);
+    HIPCHK(hipMemcpy(e->d_wave_key.p, &none, 8, hipMemcpyHostToDevice));
+  }
 }
 
 // grow a partition set's instance arena to hold `keys` keys (blocks are key-major: a prefix copy)
@@ -448,6 +491,9 @@ void part_grow(sdh_engine* e, sdh_engine::PartSet& ps, int64_t keys) {
 
 namespace {
 
+// the most partials one K_wave query holds (K_part's limit is 65,536 per instance)
+constexpr int WAVE_MAX_CAP = 1 << 20;
+
 // the sizing after a K_gen capacity failure of kinds `capk` (kg::CAP_*): each limit hit doubles
 bool gen_grown_sizing(const sdh_engine* e, int capk, kg::Sizing* out) {
   kg::Sizing sz = e->gsz;
@@ -503,6 +549,30 @@ void part_grow_cap(sdh_engine* e, sdh_engine::PartSet& ps) {
                           hipMemcpyDeviceToDevice, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   ps.st.swap(nst);
+}
+
+// K_wave tables at `cap` entries: every table keeps its header and pages at the same word offsets
+// (pages are page-major: a prefix copy per table). HBM exhaustion is SDH_E_CAPACITY, as elsewhere
+void wave_grow_cap(sdh_engine* e, sdh_engine::WaveSet& ws, int cap) {
+  const int64_t ostride = ws.stride();
+  const size_t nq = ws.qs.size();
+  ws.cap = cap;
+  const int64_t nstride = ws.stride();
+  for (auto& b : ws.st) {
+    int64_t* q = nullptr;
+    if (hipMalloc(&q, nq * (size_t)nstride * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      throw Error(SDH_E_CAPACITY, fmt("device memory exhausted growing the K_wave tables to %d partials per query", cap));
+    }
+    DevBuf<int64_t> nb;
+    nb.p = q;
+    nb.n = nq * (size_t)nstride;
+    HIPCHK(hipMemsetAsync(nb.p, 0, nb.n * 8, e->stream));
+    HIPCHK(hipMemcpy2DAsync(nb.p, (size_t)nstride * 8, b.p, (size_t)ostride * 8, (size_t)ostride * 8, nq,
+                            hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    b.swap(nb);
+  }
 }
 
 // keys this push created (ids [nk_seen, new_n)), in the order of their first events: the order
@@ -913,6 +983,41 @@ void part_sets(Pass& p, int pi, const sdh_engine::Route& rt, Routed r) {
   }
 }
 
+// K_wave: the stream's set, one wave per query (nfa_wave.hip). It reads st[cur] and writes st[1 - cur]
+void wave_sets(Pass& p) {
+  sdh_engine* e = p.e;
+  if (p.B.n <= 0) return;
+  for (size_t si = 0; si < e->wsets.size(); ++si) {
+    auto& ws = *e->wsets[si];
+    if (ws.stream != p.stream) continue;
+    sdh::WaveLaunch W{};
+    W.tab = tables_of(e);
+    W.qlist = ws.d_qs.p;
+    W.b = p.B;
+    W.n_items = (int32_t)ws.qs.size();
+    W.cap = ws.cap;
+    W.ew = ws.ew;
+    W.cmax = ws.cmax;
+    W.n_e1 = ws.n_e1;
+    W.n_first = ws.n_first;
+    W.n_last = ws.n_last;
+    W.na = ws.na;
+    W.in = ws.st[ws.cur].p;
+    W.out = ws.st[1 - ws.cur].p;
+    W.sink = sink_of(e, p.write);
+    W.wide = sdh::knob("SDH_KWAVE_WIDE") ? 1 : 0;
+    W.xcd = e->xcd;
+    W.err = e->d_werr.p + 4 * si;
+    HIPCHK(sdh_launch_wave(&W, e->stream));
+    e->wave_items += W.n_items;
+    ws.ran = true;
+    p.any = true;
+    // every query stages the batch once; a tile's walk reads and writes the live pages (not modelled:
+    // they depend on the data)
+    p.bytes += (double)p.B.n * p.ev_bytes * W.n_items;
+  }
+}
+
 // the partition's K_slab sets: item = (key segment, group whose shape reads this stream)
 void slab_sets(Pass& p, int pi, const sdh_engine::Route& rt, Routed r) {
   sdh_engine* e = p.e;
@@ -1036,7 +1141,7 @@ void partition_pass(Pass& p, int pi) {
   slab_sets(p, pi, rt, r);
 }
 
-// One pass of every K_gen / K_seq / K_part / K_slab launch of a push over `stream` (partition routing,
+// One pass of every K_gen / K_seq / K_wave / K_part / K_slab launch of a push over `stream` (partition routing,
 // arena growth, kernels, the event-chunk copy-backs). Returns whether anything ran; *tail_new_len is set
 // to the stream's K_seq tail length once the pass is accepted, if a K_seq launch ran.
 bool gen_pass(sdh_engine* e, int stream, const StreamBatch& B, bool write, double* bytes_out, int32_t* tail_new_len) {
@@ -1048,6 +1153,9 @@ bool gen_pass(sdh_engine* e, int stream, const StreamBatch& B, bool write, doubl
   e->stats.last_part_items = 0;
   for (auto& gs : e->gsets)
     if (gs->partition < 0) unpartitioned_pass(p, *gs);
+  e->wave_items = 0;
+  wave_sets(p);
+  e->stats.last_gen_items += e->wave_items;  // (K_wave's items, a wave each, count with K_gen's)
   for (int pi = 0; pi < (int)e->routes.size(); ++pi)
     if (e->routes[pi]) partition_pass(p, pi);
   if (p.tail_new_len >= 0) *tail_new_len = p.tail_new_len;
@@ -1063,7 +1171,7 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
   *bytes_out = 0;
   e->stats.last_gen_items = 0;
   e->stats.last_seq_items = 0;
-  if (e->gsets.empty() && e->psets.empty() && e->ssets.empty()) return;
+  if (e->gsets.empty() && e->psets.empty() && e->ssets.empty() && e->wsets.empty()) return;
   const int64_t n = B.n;
   e->g_out_cap = std::max<int64_t>(e->g_out_cap, std::max<int64_t>(1 << 22, n * 64));
   static_assert((1 << 22) > 2 * GEN_RING_MARGIN, "ring capacity");
@@ -1086,12 +1194,15 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
   float ms = 0;
   const size_t nps = e->psets.size();
   std::vector<int32_t> perr(4 * std::max<size_t>(1, nps), 0);
+  const size_t nws = e->wsets.size();
+  std::vector<int32_t> werr(4 * std::max<size_t>(1, nws), 0);
   for (int attempt = 0;; ++attempt) {
     e->g_out.ensure((size_t)e->g_out_cap);
     if (write) e->g_rec_off.ensure((size_t)rec_cap_of(e));
     HIPCHK(hipMemsetAsync(e->d_err.p, 0, 16, e->stream));
     HIPCHK(hipMemsetAsync(e->d_perr.p, 0, perr.size() * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->d_serr.p, 0, serr.size() * 4, e->stream));
+    if (nws) HIPCHK(hipMemsetAsync(e->d_werr.p, 0, werr.size() * 4, e->stream));
     e->slab_items = 0;
     HIPCHK(hipMemsetAsync(e->g_out_next.p, 0, 8, e->stream));
     HIPCHK(hipMemsetAsync(e->g_nrec.p, 0, 8, e->stream));
@@ -1102,6 +1213,7 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
     HIPCHK(hipMemcpyAsync(errs, e->d_err.p, 16, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(perr.data(), e->d_perr.p, perr.size() * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(serr.data(), e->d_serr.p, serr.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    if (nws) HIPCHK(hipMemcpyAsync(werr.data(), e->d_werr.p, werr.size() * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(&nrec, e->g_nrec.p, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(&used, e->g_out_next.p, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -1115,13 +1227,18 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
       out_over |= serr[4 * i + 2] != 0;
       slab_over |= serr[4 * i] != 0 || serr[4 * i + 1] != 0;
     }
+    bool wave_over = false;
+    for (size_t i = 0; i < nws; ++i) {
+      out_over |= werr[4 * i + 2] != 0;
+      wave_over |= werr[4 * i] != 0;
+    }
     kg::Sizing grown;
     const bool pools_over = errs[0] != 0 && gen_grown_sizing(e, errs[0], &grown);
     if (sdh::knob("SDH_TRACE"))
       fprintf(stderr, "[sdh] gen pass stream %d n %lld attempt %d: out %d part %d pools %d slab %d, %llu of %lld words, %.2f ms\n",
               stream, (long long)n, attempt, (int)out_over, (int)part_over, (int)pools_over, (int)slab_over, used,
               (long long)e->g_out_cap, ms);
-    if ((out_over || part_over || pools_over || slab_over) && e->g_journal && attempt < 24 &&
+    if ((out_over || part_over || pools_over || slab_over || wave_over) && e->g_journal && attempt < 24 &&
         (!errs[0] || pools_over) && !errs[1] && !errs[3]) {
       // undo the pass (K_gen blocks from the journal; K_part tables are double-buffered and their
       // per-key selectors are swapped only after success) and re-run it with room for every match
@@ -1157,6 +1274,17 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
           part_grow_cap(e, *e->psets[i]);
           ++e->part_regrows;
         }
+      // K_wave: the pass wrote the other table of each pair, so there is nothing to undo; the tables
+      // grow to the walk's upper bound of what they need (at least double) and the pass runs again
+      for (size_t i = 0; i < nws; ++i)
+        if (werr[4 * i]) {
+          auto& ws = *e->wsets[i];
+          if (ws.cap >= WAVE_MAX_CAP)
+            throw Error(SDH_E_CAPACITY, fmt("more than %d pending partials in one K_wave query", WAVE_MAX_CAP));
+          const int64_t want = std::max<int64_t>(2 * (int64_t)ws.cap, ((int64_t)werr[4 * i + 3] + 63) / 64 * 64);
+          wave_grow_cap(e, ws, (int)std::min<int64_t>(want, WAVE_MAX_CAP));
+          ++e->wave_regrows;
+        }
       continue;
     }
     if (part_over)
@@ -1164,6 +1292,7 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
     if (out_over)
       throw Error(SDH_E_CAPACITY, "K_gen match output overflow (no room for an exact re-run)");
     if (slab_over) throw Error(SDH_E_CAPACITY, "K_slab capacity (no room for an exact re-run)");
+    if (wave_over) throw Error(SDH_E_CAPACITY, "K_wave partial table overflow (no room for an exact re-run)");
     break;
   }
   // the push succeeded: its K_slab allocations are committed (the heads tell the next push's room)
@@ -1181,6 +1310,11 @@ void launch_gen(sdh_engine* e, int stream, const StreamBatch& B, double* ms_out,
     if (pp->ran) {
       pp->cur.swap(pp->nxt);
       pp->ran = false;
+    }
+  for (auto& wp : e->wsets)  // and so do the K_wave tables
+    if (wp->ran) {
+      wp->cur ^= 1;
+      wp->ran = false;
     }
   if (tail_len >= 0 && !errs[0] && !errs[1] && !errs[3]) {
     HIPCHK(sdh_seq_tail(&B, e->seq_tail[stream].p, e->seq_tail_len[stream], tail_len, e->stream));
@@ -1309,6 +1443,74 @@ void snap_load_part(sdh_engine* e, snap::Reader& r) {
     get_dev(r, ps.st.p, (size_t)2 * ps.key_cap * ps.n_groups * ps.bw() * 64 * 8);
     get_dev(r, ps.cur.p, (size_t)ps.key_cap * 4);
   }
+}
+
+// K_wave tables: per set its stream, queries, layout and capacity, then each query's current table
+// (the other one of a pair is scratch until the next push writes it)
+void snap_save_wave(sdh_engine* e, snap::Writer& w) {
+  w.put((int64_t)e->wsets.size());
+  for (auto& wp : e->wsets) {
+    auto& ws = *wp;
+    w.put(ws.stream);
+    w.put((int64_t)ws.qs.size());
+    w.put(ws.ew);
+    w.put(ws.cap);
+    put_dev(w, ws.st[ws.cur].p, ws.qs.size() * (size_t)ws.stride() * 8);
+  }
+}
+
+void snap_load_wave(sdh_engine* e, snap::Reader& r) {
+  snap::need((size_t)r.get() == e->wsets.size(), "snapshot of a different program");
+  // every set's section is checked before any table is uploaded: the kernel trusts a table's live
+  // count and each live entry's chain length
+  struct Sec { int64_t cap; const int64_t* blob; };
+  std::vector<Sec> secs;
+  for (auto& wp : e->wsets) {
+    auto& ws = *wp;
+    snap::need(r.get() == ws.stream && (size_t)r.get() == ws.qs.size() && r.get() == ws.ew,
+               "snapshot of a different program");
+    const int64_t cap = r.get();
+    snap::need(cap >= 64 && cap % 64 == 0 && cap <= WAVE_MAX_CAP, "bad snapshot K_wave table size");
+    const size_t stride = (size_t)(WV_HDR + cap * ws.ew);
+    const int64_t* blob = (const int64_t*)r.bytes(ws.qs.size() * stride * 8);
+    for (size_t qx = 0; qx < ws.qs.size(); ++qx) {
+      const int64_t* t = blob + qx * stride;
+      const int64_t n = t[0], cmax = e->gq[ws.qs[qx]].st[1].max;
+      snap::need(n >= 0 && n <= cap, "bad snapshot K_wave live count");
+      for (int64_t i = 0; i < n; ++i) {  // entry i's flags word: word 2 of lane i % 64 of page i / 64
+        const int64_t fl = t[WV_HDR + ((i >> 6) * ws.ew + 2) * 64 + (i & 63)];
+        snap::need((fl & 0xff) <= cmax, "bad snapshot K_wave chain length");
+      }
+    }
+    secs.push_back({cap, blob});
+  }
+  for (size_t si = 0; si < e->wsets.size(); ++si) {
+    auto& ws = *e->wsets[si];
+    const size_t words = ws.qs.size() * (size_t)(WV_HDR + secs[si].cap * ws.ew);
+    if (secs[si].cap != ws.cap) {
+      ws.cap = (int)secs[si].cap;
+      for (auto& b : ws.st) {
+        DevBuf<int64_t>().swap(b);  // freed: reallocated at the snapshot's capacity
+        b.ensure(words);
+      }
+    }
+    ws.cur = 0;
+    ws.ran = false;
+    HIPCHK(hipMemcpy(ws.st[0].p, secs[si].blob, words * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(ws.st[1].p, 0, words * 8));
+  }
+}
+
+// live partials of the K_wave tables (sdh_engine_stats)
+int64_t wave_live_partials(sdh_engine* e) {
+  if (e->wsets.empty()) return 0;
+  unsigned long long* acc = e->d_wave_live.p;  // (allocated once, at creation)
+  HIPCHK(hipMemsetAsync(acc, 0, 8, e->stream));
+  for (auto& wp : e->wsets)
+    HIPCHK(sdh_live_wave(wp->st[wp->cur].p, (int64_t)wp->qs.size(), wp->stride(), acc, e->stream));
+  unsigned long long v = 0;
+  d2h_sync(e, &v, acc, 8);
+  return (int64_t)v;
 }
 
 // K_seq: each stream's tail (the only state its windowed sequences carry between pushes)

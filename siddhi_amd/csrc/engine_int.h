@@ -4,7 +4,7 @@
 //
 //   engine.hip          the C ABI, knobs, sdh_engine_create (plan selection); the device match table and
 //                       its polls; pushes; the multi-GPU exchange; the event store
-//   engine_gen.hip      the K_gen family (K_gen / K_seq / K_part / K_slab): sets and groups, arena and
+//   engine_gen.hip      the K_gen family (K_gen / K_seq / K_part / K_slab / K_wave): sets and groups, arena and
 //                       table growth, the journal, partition routing and the launches of a push
 //   engine_lower.hip    the callers of the host-side lowerings (chain_lower.h, select_lower.h)
 //   engine_ratchet.hip  K_chain and K_ratchet / K_gate / shared-pops launches
@@ -327,6 +327,26 @@ struct sdh_engine {
   std::vector<std::unique_ptr<PartSet>> psets;
   int64_t part_regrows = 0;          // K_part table growths so far (sdh_stats.pool_regrows)
   int part_chain_lo = 0;            // PK_CHAIN sets: the tiebreak passes their rows need (states - 1; 0: none)
+  // K_wave (nfa_wave.hip): one set per stream; a wave per query, a lane per partial. Two tables per
+  // query, st[cur] the current ones; a push writes st[1 - cur] and the host swaps once it is accepted
+  struct WaveSet {
+    int stream = 0;
+    std::vector<int32_t> qs;         // the set's queries (indices into gq), one work item each
+    DevBuf<int32_t> d_qs;
+    int cap = 64;                    // entries per table: 64 x pages (grows on overflow: wave_grow_cap). One
+                                     // capacity per set: a deep query grows every table of its stream's set
+    int ew = 3, cmax = 0, n_e1 = 0, n_first = 0, n_last = 0, na = 0;
+    int cur = 0;
+    bool ran = false;                // launched in the current pass
+    DevBuf<int64_t> st[2];           // [query][WV_HDR + cap * ew]
+    int64_t stride() const { return WV_HDR + (int64_t)cap * ew; }
+  };
+  std::vector<std::unique_ptr<WaveSet>> wsets;
+  DevBuf<int32_t> d_werr;            // per K_wave set: [0] table capacity, [2] output overflow, [3] entries needed
+  DevBuf<unsigned long long> d_wave_live;  // one word: the accumulator of wave_live_partials
+  DevBuf<int64_t> d_wave_key;        // one word, -1: the key table of the K_wave queries' narrow records
+  int64_t wave_regrows = 0;          // K_wave table growths so far (sdh_stats.pool_regrows)
+  int64_t wave_items = 0;            // K_wave work items of the last push
   // K_slab (nfa_slab.hip): one set per partition; its queries' partials as sparse entries, one block
   // per (key, group) in nsub sub-rings of a slab, found through the directory [key][group]
   struct SlabSet {
@@ -585,6 +605,8 @@ void snap_save_gen(sdh_engine* e, snap::Writer& w), snap_load_gen(sdh_engine* e,
 void snap_save_routes(sdh_engine* e, snap::Writer& w), snap_load_routes(sdh_engine* e, snap::Reader& r);
 void snap_save_part(sdh_engine* e, snap::Writer& w), snap_load_part(sdh_engine* e, snap::Reader& r);
 void snap_save_seq(sdh_engine* e, snap::Writer& w), snap_load_seq(sdh_engine* e, snap::Reader& r);
+void snap_save_wave(sdh_engine* e, snap::Writer& w), snap_load_wave(sdh_engine* e, snap::Reader& r);
+int64_t wave_live_partials(sdh_engine* e);
 // engine_ratchet.hip
 void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2],
             const std::vector<int>& qs, bool allow_chunks, bool* unordered);

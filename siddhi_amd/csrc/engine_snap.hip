@@ -20,14 +20,20 @@ namespace eng {
 //   seq       n_streams; per stream: tail length, tail[SEQ_TMAX x SEQ_TW]
 //   slab      n_sets; per set: partition, key_cap, n_groups, lds_words, words, dir[key_cap x n_groups]
 //             (pointing into:) the live blocks packed into one ring[words] (4 B), live[256]
-//   events    version 9 only: cap, row words, first retained seq, then the retained rows in seq order
+//   events    versions 9 and 11 only: cap, row words, first retained seq, then the retained rows in seq order
+//   wave      versions 10 and 11 only (an engine with K_wave queries): n_sets; per set: stream, queries,
+//             entry words, cap, the queries' current tables [queries][WV_HDR + cap x entry words]
+// An engine without K_wave queries writes versions 8 / 9, byte for byte what it wrote before the wave
+// section existed; one with K_wave queries writes 10 / 11: the same layout followed by `wave`.
 constexpr int64_t SNAP_MAGIC = 0x5344485350415254LL;
 constexpr int64_t SNAP_VERSION = 8;
 constexpr int64_t SNAP_VERSION_EVENTS = 9;  // version 8 followed by the event store (sdh_engine_retain_events)
+constexpr int64_t SNAP_VERSION_WAVE = 10;   // version 8 / 9 followed by the wave section: 10 / 11
 
 void snap_save(sdh_engine* e, snap::Writer& w) {
   w.put(SNAP_MAGIC);
-  w.put(e->ev_cap ? SNAP_VERSION_EVENTS : SNAP_VERSION);  // (an engine that keeps events writes version 9)
+  // (an engine that keeps events writes version 9; K_wave queries add the wave section: 10 / 11)
+  w.put((e->ev_cap ? SNAP_VERSION_EVENTS : SNAP_VERSION) + (e->wsets.empty() ? 0 : SNAP_VERSION_WAVE - SNAP_VERSION));
   w.put((int64_t)e->lq.size());
   w.put(e->pcap);
   w.put(e->gB32);
@@ -48,6 +54,7 @@ void snap_save(sdh_engine* e, snap::Writer& w) {
   snap_save_seq(e, w);
   snap_save_slab(e, w);
   if (e->ev_cap) snap_save_events(e, w);
+  if (!e->wsets.empty()) snap_save_wave(e, w);
 }
 
 // Nothing changes before every check that needs no change has passed: a blob refused by then leaves the
@@ -57,7 +64,11 @@ void snap_load(sdh_engine* e, snap::Reader r) {
   using snap::need;
   need(r.get() == SNAP_MAGIC, "bad snapshot magic");
   const int64_t version = r.get();
-  need(version == SNAP_VERSION || version == SNAP_VERSION_EVENTS, "snapshot of another format version");
+  // this engine's versions: with K_wave queries 10 / 11, without 8 / 9 (a blob of the other pair is
+  // of another program's plans: refused here, before anything changes)
+  const int64_t vbase = e->wsets.empty() ? SNAP_VERSION : SNAP_VERSION_WAVE;
+  need(version == vbase || version == vbase + 1, "snapshot of another format version");
+  const bool stored = version == vbase + 1;
   const size_t nq = (size_t)r.get();
   const int64_t spcap = r.get();  // the snapshot's K_chain table capacity
   need(nq == e->lq.size() && spcap >= 64 && spcap % 64 == 0 && spcap <= (1 << 24), "snapshot of a different program");
@@ -87,7 +98,8 @@ void snap_load(sdh_engine* e, snap::Reader r) {
     snap_load_part(e, r);
     snap_load_seq(e, r);
     snap_load_slab(e, r);
-    snap_load_events(e, r, version == SNAP_VERSION_EVENTS);
+    snap_load_events(e, r, stored);
+    if (!e->wsets.empty()) snap_load_wave(e, r);
   } catch (...) {
     e->broken = "a failed restore";
     throw;

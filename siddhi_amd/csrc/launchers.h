@@ -17,6 +17,7 @@ struct RatchetLaunch;
 struct SharedLaunch;
 struct GenLaunch;
 struct PartLaunch;
+struct WaveLaunch;
 struct SlabLaunch;
 struct SeqLaunch;
 struct MatchTable;
@@ -48,6 +49,10 @@ extern "C" hipError_t sdh_launch_gen(const sdh::GenLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_part(const sdh::PartLaunch* L, hipStream_t s);
 // the interpreted kernel of K_part's chain kind (nfa_part_chain.hip; sdh_launch_part hands PK_CHAIN on)
 extern "C" hipError_t sdh_launch_part_chain(const sdh::PartLaunch* L, hipStream_t s);
+// K_wave (nfa_wave.hip): one wave per unpartitioned count query, and the live entries of n tables
+// (their header words, summed into acc)
+extern "C" hipError_t sdh_launch_wave(const sdh::WaveLaunch* L, hipStream_t s);
+extern "C" hipError_t sdh_live_wave(const int64_t* st, int64_t n, int64_t stride, unsigned long long* acc, hipStream_t s);
 extern "C" hipError_t sdh_launch_seq(const sdh::SeqLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_slab(const sdh::SlabLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_slab_rollback(uint64_t* dir, const uint64_t* journal, const uint64_t* journal_idx, int64_t n,

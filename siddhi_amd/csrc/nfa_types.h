@@ -482,6 +482,36 @@ struct PartLaunch {
 };
 
 // ------------------------------------------------------------------------------------------
+// K_wave launch (nfa_wave.hip): unpartitioned count patterns, one wave per query, one lane per partial
+//   every e1=S[f1] -> e2=S[f2] <min:max> -> e3=S[f3(e1, e2[0], e2[last], cur)] [within T]
+// item = query. Its table = [WV_HDR header words][pages][ew entry words][64 lanes] (int64): entry i is
+// lane i % 64 of page i / 64, its word w at WV_HDR + ((i / 64) * ew + w) * 64 + i % 64 -- a page is
+// loaded and stored field-major, one coalesced 512-B access per word. Entries use the PK_COUNT layout
+// with the set's widest cmax / captured words. Two tables per query (`in` before the push, `out` after
+// it): the host swaps them once the pass is accepted, so an overflow re-runs the push exactly.
+// Records: the PK_COUNT narrow record with key id 0 (the engine's one-word key table holds -1), or
+// the K_gen record with key -1.
+// ------------------------------------------------------------------------------------------
+constexpr int WV_HDR = 8;      // header words: [0] entries, [1] the pending-list entries they stand for (sdh_stats.live_partials)
+struct WaveLaunch {
+  GroupTables tab;            // tab.queries: the engine's queries
+  const int32_t* qlist;       // [n_items] the items' queries (indices into tab.queries)
+  StreamBatch b;
+  int32_t n_items;
+  int32_t cap;                // entries per table (64 x pages)
+  int32_t ew;                 // words per entry
+  int32_t cmax;               // chain words per entry (the set's largest max)
+  int32_t n_e1, n_first, n_last;  // captured words stored per entry (0 or the set's widest n_cap)
+  int32_t na;                 // captured words staged per event (the set's widest n_cap)
+  const int64_t* in;          // [n_items][WV_HDR + cap * ew]
+  int64_t* out;
+  RecordSink sink;
+  int32_t wide;               // every match as a K_gen record (SDH_KWAVE_WIDE, the > int32 path)
+  int32_t xcd;                // items in per-XCD ranges (as PartLaunch)
+  int32_t* err;               // [0] table capacity, [2] output overflow, [3] entries that fit every table (an upper bound, nfa_wave.hip)
+};
+
+// ------------------------------------------------------------------------------------------
 // K_slab launch (nfa_slab.hip): distinct-stream patterns on sparse per-partial entries (slab.h)
 // item = (key segment of the pushed stream, group from glist); block (kid, g) = dir[kid * groups + g]
 // in sub-ring sub_of(kid * groups + g) (a separately allocated ring buffer)

@@ -78,29 +78,88 @@ inline KPart kpart_chain_shape(const kg::LQuery& q, const kg::GQuery& g) {
   return k;
 }
 
+// The checks of kpart_shape, in its order, as steps a sibling selector shares (wave_lower.h: the same
+// count shape without its partition). Each returns nullptr, or why the query is not that shape.
+
+// what every K_part shape needs of a pattern query whatever its states are
+inline const char* kpart_pattern_why(const kg::LQuery& q, const kg::GQuery& g) {
+  for (const auto& x : q.st)
+    if (x.waiting != -1) return "an absent side";  // absent sides run on K_gen
+  // start ids exist only with `within` (StateInputStreamParser.java:126-138): then e1 alone
+  if (!(q.start_ids.empty() || (q.start_ids.size() == 1 && q.start_ids[0] == 0))) return "start states beyond e1";
+  if (g.max_depth > kg::RSTACK) return "a filter deeper than the register stack";
+  if (q.start_ids.empty() && q.within >= 0) return "`within` without start ids";
+  if (q.st.empty()) return "no states";
+  return nullptr;
+}
+
+// three states on one stream, one receiver that runs e1 first, `every` on e1 only.
+// start_within_every: e1 may name itself as its within-every state. The planner sets that link on the
+// states inside `every` of an unpartitioned query only (a partitioned one never carries it), and on
+// the start state it is inert: the link acts when a partial expires in the state that carries it, and
+// the seed e1 holds has no start-state event to expire by (kgen.h seq_lookback makes the same
+// argument). K_part passes false: its answers stay what they were for any blob.
+inline const char* kpart_three_why(const kg::LQuery& q, bool start_within_every = false) {
+  if (q.st.size() != 3) return "not three states";
+  const int s = q.st[0].stream;
+  for (size_t i = 0; i < q.st.size(); ++i) {
+    const auto& x = q.st[i];
+    const bool we_ok = x.within_every == -1 || (start_within_every && i == 0 && x.is_start && x.within_every == 0);
+    if (x.stream != s || !we_ok || x.callback != -1) return "a second stream, or a state-level within / callback";
+  }
+  if (q.recvs.size() != 1 || q.recvs[0].stream != s || q.recvs[0].procs.size() != 3 || q.recvs[0].procs[0] != 0)
+    return "not one receiver in state order";
+  const kg::LState& e1 = q.st[0];
+  if (e1.kind != kg::K_STREAM || !e1.is_start || e1.next_every != 0 || e1.has_selector) return "e1 is not the `every` start state";
+  return nullptr;
+}
+
+// states 1 and 2 are the count chain `e2=S[f2]<min:max> -> e3=S[f3]`: fills k (cmax, n_e1, n_first,
+// n_last; kind = PK_COUNT) as far as it gets
+inline const char* kpart_count_why(const kg::LQuery& q, const kg::GQuery& g, KPart& k) {
+  const kg::LState &e1 = q.st[0], &c = q.st[1], &e3 = q.st[2];
+  const auto& procs = q.recvs[0].procs;
+  if (c.kind != kg::K_COUNT) return c.kind == kg::K_LOGICAL ? "a logical state" : "no count state in the middle";
+  if (c.min < 1) return "count min below 1";
+  if (c.max == INT32_MAX) return "an unbounded count";  // (`<n:>`: the planner's Integer.MAX_VALUE)
+  if (c.max > PK_CMAX) return "count max beyond PK_CMAX";
+  if (c.min > c.max) return "count min above max";
+  if (c.next_pre != 2 || c.next_every != -1 || c.has_selector || e1.next_pre != 1) return "the count state is not the middle state";
+  if (e3.kind != kg::K_STREAM || e3.next_pre != -1 || e3.next_every != -1 || !e3.has_selector) return "e3 is not the last stream state";
+  if (procs[1] != 1 || procs[2] != 2) return "not one receiver in state order";
+  std::vector<std::pair<int64_t, int64_t>> r;
+  filter_refs(c, r);  // the count filter reads only the event it is appending (CURRENT)
+  for (const auto& x : r)
+    if (x.first != 1 || x.second != -1) return "f2 reads more than the current event";
+  r.clear();
+  filter_refs(e3, r);  // e3 reads e1, e2[0], e2[last] (= CURRENT of another state) and itself
+  const int ncap = g.n_cap[q.st[0].stream];
+  for (const auto& x : r) {
+    if (x.first == 1) {
+      if (x.second == 0) k.n_first = ncap;
+      else if (x.second == -1) k.n_last = ncap;
+      else return "f3 reads a chain event other than e2[0] / e2[last]";
+    } else if (x.first == 0) {
+      k.n_e1 = ncap;
+    }
+  }
+  k.cmax = c.max;
+  k.kind = PK_COUNT;
+  return nullptr;
+}
+
 inline KPart kpart_shape(const kg::LProgram& P, int qi, const kg::GQuery& g) {
   KPart k;
   const kg::LQuery& q = P.q[qi];
   if (q.partition < 0 || q.type != kg::Q_PATTERN) return k;
-  for (const auto& x : q.st)
-    if (x.waiting != -1) return k;  // absent sides run on K_gen
-  // start ids exist only with `within` (StateInputStreamParser.java:126-138): then e1 alone
-  if (!(q.start_ids.empty() || (q.start_ids.size() == 1 && q.start_ids[0] == 0)) || g.max_depth > kg::RSTACK) return k;
-  if (q.start_ids.empty() && q.within >= 0) return k;
-  if (q.st.empty()) return k;
+  if (kpart_pattern_why(q, g)) return k;
   {
     bool all_stream = true;
     for (const auto& x : q.st) all_stream &= x.kind == kg::K_STREAM;
     if (all_stream) return kpart_chain_shape(q, g);
   }
-  if (q.st.size() != 3) return k;
-  const int s = q.st[0].stream;
-  for (const auto& x : q.st)
-    if (x.stream != s || x.within_every != -1 || x.callback != -1) return k;
-  if (q.recvs.size() != 1 || q.recvs[0].stream != s || q.recvs[0].procs.size() != 3 || q.recvs[0].procs[0] != 0)
-    return k;
+  if (kpart_three_why(q)) return k;
   const kg::LState& e1 = q.st[0];
-  if (e1.kind != kg::K_STREAM || !e1.is_start || e1.next_every != 0 || e1.has_selector) return k;
   std::vector<std::pair<int64_t, int64_t>> r;
   const auto& procs = q.recvs[0].procs;
   if (q.st[1].kind == kg::K_LOGICAL) {
@@ -121,29 +180,7 @@ inline KPart kpart_shape(const kg::LProgram& P, int qi, const kg::GQuery& g) {
     k.kind = a.ltype == kg::L_AND ? PK_AND : PK_OR;
     return k;
   }
-  const kg::LState &c = q.st[1], &e3 = q.st[2];
-  if (c.kind != kg::K_COUNT || c.min < 1 || c.max > PK_CMAX || c.min > c.max) return k;
-  if (c.next_pre != 2 || c.next_every != -1 || c.has_selector || e1.next_pre != 1) return k;
-  if (e3.kind != kg::K_STREAM || e3.next_pre != -1 || e3.next_every != -1 || !e3.has_selector) return k;
-  if (procs[1] != 1 || procs[2] != 2) return k;
-  r.clear();
-  filter_refs(c, r);  // the count filter reads only the event it is appending (CURRENT)
-  for (const auto& x : r)
-    if (x.first != 1 || x.second != -1) return k;
-  r.clear();
-  filter_refs(e3, r);  // e3 reads e1, e2[0], e2[last] (= CURRENT of another state) and itself
-  const int ncap = g.n_cap[s];
-  for (const auto& x : r) {
-    if (x.first == 1) {
-      if (x.second == 0) k.n_first = ncap;
-      else if (x.second == -1) k.n_last = ncap;
-      else return k;
-    } else if (x.first == 0) {
-      k.n_e1 = ncap;
-    }
-  }
-  k.cmax = c.max;
-  k.kind = PK_COUNT;
+  kpart_count_why(q, g, k);  // (a declined query keeps kind -1)
   return k;
 }
 

@@ -108,7 +108,7 @@ class SdhStats(ctypes.Structure):
                 ("pool_regrows", ctypes.c_int64), ("last_slab_items", ctypes.c_int64),
                 ("placed_pushes", ctypes.c_int64), ("plan_queries", ctypes.c_int64 * 8)]
 
-PLANS = ("K_ratchet", "K_gate", "K_chain", "K_part", "K_slab", "K_seq", "K_gen")
+PLANS = ("K_ratchet", "K_gate", "K_chain", "K_part", "K_slab", "K_seq", "K_gen", "K_wave")
 
 
 EXPORTS = ["sdh_engine_create", "sdh_engine_push", "sdh_engine_flush", "sdh_engine_poll", "sdh_engine_poll_device",

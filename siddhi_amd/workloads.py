@@ -147,6 +147,20 @@ def c3_app(n_patterns: int, first: int = 0, step: int = 1) -> str:
     return f"{STOCK_STREAM} partition with (symbol of StockStream) begin {qs} end;"
 
 
+def c3w_query(p: int, seed: int = PATTERN_SEED) -> str:
+    """The C3 family's count shape without its partition (tools/wave_bench.py; K_wave):
+    pattern p's thresholds as c3_query's count kind has them, over the whole stream."""
+    t = c2_threshold_text(p)
+    v = 100 + (splitmix64(seed ^ (p + 1000)) % 800)
+    return (f"@info(name='w{p}') from every e1=StockStream[price > {t}] -> e2=StockStream[volume > {v // 4}] <2:5> -> "
+            f"e3=StockStream[price > e2[last].price] within 10 sec "
+            f"select e1.price as a, e2[0].volume as b, e3.price as c insert into OutStream;")
+
+
+def c3w_app(n_patterns: int) -> str:
+    return STOCK_STREAM + " " + " ".join(c3w_query(p) for p in range(n_patterns))
+
+
 TXN_STREAM = "define stream Txn (account string, amount float, risk int);"
 
 
