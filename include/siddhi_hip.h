@@ -11,6 +11,10 @@
  *   sdh_engine_push     <- stream/StreamJunction.java:376-389 (Receiver.receive(Event[]) /
  *                          receive(long, Object[])) -> query/input/ProcessStreamReceiver.java:105-183
  *                          -> state/StreamPreStateProcessor.java:292-337 (processAndReturn)
+ *   sdh_engine_push_mixed  <- the same seam for a feed that interleaves several junctions event by
+ *                          event (each event still goes through its own stream's
+ *                          StreamJunction.java:376-389 receive, in arrival order): one call carries
+ *                          the events of several streams and the order they arrived in
  *   sdh_engine_poll     <- query/input/SingleProcessStreamReceiver.java:75-79 and
  *                          query/input/StateMultiProcessStreamReceiver.java:65-72 (hand-off of each
  *                          completed StateEvent to QuerySelector.process)
@@ -213,6 +217,38 @@ typedef struct sdh_stats {
 
 int sdh_engine_create(const void* ir_blob, size_t len, const sdh_config* cfg, sdh_engine** out);
 int sdh_engine_push(sdh_engine* e, int32_t stream, const sdh_batch* batch);
+/* Interleaved multi-stream push: the events of several streams in one call, in the order they
+ * arrived. Replaces the same seam as sdh_engine_push (StreamJunction.java:376-389 per event) for a feed
+ * that interleaves streams event by event, which would otherwise be cut into one sdh_engine_push per
+ * maximal same-stream run.
+ *   parts[p]   one stream's events of the call: its batch (chunk == 0) and its stream; no stream twice;
+ *              every part host-resident or every part device-resident; empty parts are allowed.
+ *   order[k]   the index into `parts` of the k-th event of the call, n_order = the sum of the parts' n;
+ *              the i-th occurrence of p in `order` is event i of parts[p].batch. A host array, or with
+ *              order_on_device != 0 a HIP device pointer whose contents are complete.
+ * The call is observably identical to pushing each maximal same-part run of `order` with
+ * sdh_engine_push (chunk == 0, per-event sends), in order: the same matches in the same delivery order,
+ * the same sequence numbers (the k-th event of the call has seq = events pushed before + k), the same
+ * sdh_stats.events / pattern_events / matches, and the same state for every later call (snapshot bytes
+ * need not be equal). n_order == 0 is a no-op.
+ * SDH_E_INVALID, with nothing changed: a stream named twice, a part with chunk != 0 or with a column
+ * count that is not its stream's, mixed on_device among the parts, n_order != the sum of the parts' n, a
+ * part whose count in `order` is not its n (or an order value outside [0, n_parts)), a total above
+ * max_batch.
+ * Two paths (DESIGN.md §3.2 "Interleaved pushes"). Native: one K_chain launch over the merged sequence,
+ * taken when every query that reads a named stream is a K_chain query (no K_ratchet / K_gate group and
+ * no K_gen-family or K_wave set reads one), no communicator is set, and at most 8 parts are named.
+ * Otherwise the engine itself splits the call into its runs and pushes each. With SDH_FLAG_DEVICE_MATCHES
+ * a run push would drop the records of the run before it, so there a call that cannot run natively
+ * fails with SDH_E_UNSUPPORTED, nothing changed; a native call's device records are one segment set,
+ * as after sdh_engine_push. */
+typedef struct sdh_mixed_part {
+  int32_t stream;
+  int32_t reserved;          /* 0 */
+  sdh_batch batch;
+} sdh_mixed_part;
+int sdh_engine_push_mixed(sdh_engine* e, int32_t n_parts, const sdh_mixed_part* parts, const int32_t* order,
+                          int64_t n_order, int32_t order_on_device);
 int sdh_engine_flush(sdh_engine* e);
 int sdh_engine_poll(sdh_engine* e, sdh_matches* out);
 /* As sdh_engine_poll, but every sdh_matches pointer is a HIP device pointer into engine-owned HBM
@@ -496,6 +532,10 @@ int sdh_engine_debug_digest(sdh_engine* e, uint64_t* out);
 /* Test diagnostic: *out = the pushes so far whose K_ratchet records were written by the shared-pops
  * form (the pops computed once per push; SDH_RATCHET_SHARED_MIN / SDH_RATCHET_NO_SHARED in debug). */
 int sdh_engine_debug_shared_pushes(sdh_engine* e, int64_t* out);
+/* Test diagnostic: out[0] = the sdh_engine_push_mixed calls so far that ran natively (one K_chain launch
+ * over the merged sequence), out[1] = those the engine split into run pushes (SDH_MIX_SPLIT=1 in debug
+ * forces that path). No-op calls (n_order == 0) and refused calls count in neither. */
+int sdh_engine_debug_mixed_pushes(sdh_engine* e, int64_t* out /* 2 entries */);
 /* Diagnostic: best-of-`iters` HBM bandwidth of a streaming copy (bytes read + written) and a
  * streaming read over `bytes`-sized buffers on `device`, in GB/s -- the measured ceiling the bench
  * reports its roofline fraction against beside the 8 TB/s peak. */

@@ -654,6 +654,330 @@ int do_push(sdh_engine* e, int32_t stream, const sdh_batch* b) {
   return SDH_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Interleaved pushes (sdh_engine_push_mixed; DESIGN.md §3.2 "Interleaved pushes")
+// ------------------------------------------------------------------------------------------
+struct MixRun {
+  int part;
+  int64_t off, n;  // events [off, off + n) of the part
+};
+
+// the maximal same-part runs of a host `order` (values already checked)
+std::vector<MixRun> mix_runs(const int32_t* order, int64_t n, int n_parts) {
+  std::vector<MixRun> runs;
+  std::vector<int64_t> used((size_t)n_parts, 0);
+  for (int64_t k = 0; k < n;) {
+    const int p = order[k];
+    int64_t k1 = k;
+    while (k1 < n && order[k1] == p) ++k1;
+    runs.push_back({p, used[p], k1 - k});
+    used[p] += k1 - k;
+    k = k1;
+  }
+  return runs;
+}
+
+// the split path: each run is a contiguous slice of its part, pushed as do_push's own journal split
+// pushes its halves
+void mix_split(sdh_engine* e, const sdh_mixed_part* parts, const std::vector<MixRun>& runs) {
+  for (const MixRun& r : runs) {
+    const sdh_batch& b = parts[r.part].batch;
+    const int stream = parts[r.part].stream;
+    const auto& types = e->prog.stream_types[stream];
+    const int na = (int)types.size();
+    std::vector<const void*> cols(na);
+    std::vector<const uint8_t*> nl(na);
+    for (int a = 0; a < na; ++a) {
+      cols[a] = (const uint8_t*)b.cols[a] + r.off * attr_width(types[a]);
+      nl[a] = (b.nulls && b.nulls[a]) ? b.nulls[a] + r.off : nullptr;
+    }
+    sdh_batch v = b;
+    v.n = r.n;
+    v.ts = b.ts + r.off;
+    v.cols = cols.data();
+    v.nulls = b.nulls ? nl.data() : nullptr;
+    do_push(e, stream, &v);
+  }
+}
+
+// every consumer of the named streams is a K_chain query, and nothing else stands in the way
+bool mix_native_ok(const sdh_engine* e, int n_parts, const sdh_mixed_part* parts, int64_t total) {
+  const char* k = sdh::knob("SDH_MIX_SPLIT");
+  if ((k && atoi(k) != 0) || e->comm || n_parts > MIX_MAXP || total >= INT32_MAX) return false;
+  for (const auto& gs : e->gsets)
+    if (gs->timed) return false;  // absent states: time passes for the set on every push, whatever its stream
+  for (int p = 0; p < n_parts; ++p) {
+    const int s = parts[p].stream;
+    for (const auto& g : e->rg)
+      if (g.stream == s) return false;  // K_ratchet / K_gate
+    for (const auto& g : e->gq)         // the K_gen family, K_wave included
+      if (s >= kg::GMAXSTREAM || g.recv_n[s] > 0) return false;
+  }
+  return true;
+}
+
+// the native path: pre-pass, one K_chain launch over the merged sequence, the table append and the
+// event store from the merged positions. cnt: the parts' events; order: host or device (order_dev)
+void mix_native(sdh_engine* e, int n_parts, const sdh_mixed_part* parts, const int32_t* order, int64_t total,
+                bool order_dev, bool counted) {
+  const bool on_dev = parts[0].batch.on_device != 0;
+  const int ns = (int)e->prog.stream_types.size();
+  MixLaunch ML{};
+  MixPre A{};
+  ML.n_parts = A.n_parts = n_parts;
+  std::vector<int32_t> pstream((size_t)ns, -1);
+  std::vector<int64_t> last_ts((size_t)n_parts, 0);
+  int64_t off = 0;
+  for (int p = 0; p < n_parts; ++p) {
+    const sdh_batch& b = parts[p].batch;
+    const int stream = parts[p].stream;
+    const auto& types = e->prog.stream_types[stream];
+    StreamBatch& B = ML.parts[p];
+    B.n = b.n;
+    B.n_attr = (int)types.size();
+    B.stream = stream;
+    B.seq_base = e->seq;
+    B.prev_ts = e->prev_ts[stream];
+    for (int a = 0; a < B.n_attr; ++a) B.width[a] = attr_width(types[a]);
+    pstream[stream] = p;
+    A.part_n[p] = b.n;
+    A.pos_off[p] = off;
+    off += b.n;
+    if (b.n == 0) continue;
+    if (on_dev) {
+      B.ts = b.ts;
+      for (int a = 0; a < B.n_attr; ++a) {
+        B.col[a] = b.cols[a];
+        B.nul[a] = b.nulls ? b.nulls[a] : nullptr;
+      }
+    } else {
+      // (stage_host_batch fills d_batch: each part keeps its own buffer)
+      e->d_batch.swap(e->d_mix_batch[p]);
+      try {
+        stage_host_batch(e, &b, B);
+      } catch (...) {
+        e->d_batch.swap(e->d_mix_batch[p]);
+        throw;
+      }
+      e->d_batch.swap(e->d_mix_batch[p]);
+      last_ts[p] = b.ts[b.n - 1];
+    }
+    A.ts[p] = B.ts;
+  }
+  // ---- pre-pass ----
+  const int64_t nb = sdh_mix_blocks(total);
+  e->d_mix_idx.ensure((size_t)total);
+  e->d_mix_pos.ensure((size_t)total);
+  e->d_mix_ts.ensure((size_t)total);
+  e->d_mix_cnt.ensure((size_t)nb * MIX_MAXP);
+  e->d_mix_total.ensure(MIX_MAXP);
+  e->d_mix_err.ensure(1);
+  if (!order_dev) {
+    e->d_mix_order.ensure((size_t)total);
+    HIPCHK(hipMemcpyAsync(e->d_mix_order.p, order, (size_t)total * 4, hipMemcpyHostToDevice, e->stream));
+    order = e->d_mix_order.p;
+  }
+  A.order = order;
+  A.n = total;
+  A.blk_cnt = e->d_mix_cnt.p;
+  A.total = e->d_mix_total.p;
+  A.err = e->d_mix_err.p;
+  A.idx = e->d_mix_idx.p;
+  A.ts_out = e->d_mix_ts.p;
+  A.pos = e->d_mix_pos.p;
+  if (!counted) {  // (a device order's counts, checked by the caller before this point, left the scan behind)
+    HIPCHK(hipMemsetAsync(e->d_mix_err.p, 0, 4, e->stream));
+    HIPCHK(sdh_mix_count(&A, e->stream));
+  }
+  HIPCHK(sdh_mix_write(&A, e->stream));
+  int64_t t01[2];
+  d2h_sync(e, &t01[0], e->d_mix_ts.p, 8);
+  d2h_sync(e, &t01[1], e->d_mix_ts.p + (total - 1), 8);
+  if (on_dev)
+    for (int p = 0; p < n_parts; ++p)
+      if (parts[p].batch.n > 0) d2h_sync(e, &last_ts[p], parts[p].batch.ts + (parts[p].batch.n - 1), 8);
+  ML.order = order;
+  ML.idx = e->d_mix_idx.p;
+  e->d_mix_pstream.ensure((size_t)ns);
+  HIPCHK(hipMemcpyAsync(e->d_mix_pstream.p, pstream.data(), (size_t)ns * 4, hipMemcpyHostToDevice, e->stream));
+  ML.part_of_stream = e->d_mix_pstream.p;
+  e->d_mix.ensure(1);
+  HIPCHK(hipMemcpyAsync(e->d_mix.p, &ML, sizeof(ML), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));  // (ML and pstream are on this frame)
+  // ---- the merged batch: timestamps, count and first seq; the columns are the parts' ----
+  StreamBatch B{};
+  B.n = total;
+  B.stream = -1;
+  B.seq_base = e->seq;
+  B.prev_ts = INT64_MIN;
+  B.ts = e->d_mix_ts.p;
+  if (e->ev_cap) {
+    const int64_t first = std::max<int64_t>(0, total - e->ev_cap);
+    for (int p = 0; p < n_parts; ++p) {
+      const auto& types = e->prog.stream_types[parts[p].stream];
+      uint32_t fm = 0;
+      for (int a = 0; a < ML.parts[p].n_attr; ++a)
+        if (types[a] == T_FLOAT) fm |= 1u << a;
+      HIPCHK(sdh_store_append_mixed(&ML.parts[p], fm, e->d_mix_pos.p + A.pos_off[p], first, e->ev_rows.p, e->ev_cap - 1,
+                                    e->ev_w, e->stream));
+    }
+  }
+  // the queries that read a stream with events in this call, and what run pushes would have counted
+  std::vector<int> qs;
+  int64_t pe = 0, consumers = 0;
+  for (int li = 0; li < (int)e->lq.size(); ++li) {
+    bool reads = false;
+    for (int p = 0; p < n_parts; ++p) {
+      const auto& st = e->lq[li].streams;
+      if (parts[p].batch.n > 0 && std::find(st.begin(), st.end(), parts[p].stream) != st.end()) {
+        reads = true;
+        pe += parts[p].batch.n;
+        ++consumers;
+      }
+    }
+    if (reads) qs.push_back(li);
+  }
+  if (!e->started) {
+    e->started = true;
+    e->start_ts = t01[0];
+  }
+  // (as do_push: the previous push's device-only matches are dropped here)
+  e->work.clear();
+  e->device_matches = 0;
+  e->r_blocks_used = 0;
+  e->r_blk_taken = 0;
+  e->r_matches = 0;
+  e->r_placing = false;
+  e->r_kernel_ms = 0;
+  e->r_kernel_bytes = 0;
+  e->r_rec_bytes = 0;
+  e->r_rec4 = 0;
+  e->g_dev_matches = 0;
+  e->g_used = 0;
+  e->dev_polled = false;
+  e->last_n = total;
+  e->last_seq_base = B.seq_base;
+  e->stats.last_gen_items = 0;
+  e->stats.last_seq_items = 0;
+  auto commit_clock = [&]() {
+    for (int p = 0; p < n_parts; ++p)
+      if (parts[p].batch.n > 0) e->prev_ts[parts[p].stream] = last_ts[p];
+    e->seq += total;
+  };
+  if (!qs.empty()) {
+    e->mix = e->d_mix.p;
+    try {
+      bool unordered = false;
+      launch(e, -1, B, t01, qs, false, &unordered);
+    } catch (const std::exception& ex) {
+      e->mix = nullptr;
+      commit_clock();
+      e->broken = ex.what();
+      throw;
+    }
+    e->mix = nullptr;
+    for (int li : qs) e->cur[li] ^= 1;
+  }
+  if (consumers) {
+    e->stats.pattern_events += pe;
+    e->stats.matches += e->device_matches;
+    if (qs.empty()) e->stats.last_kernel_ms = e->stats.last_kernel_bytes = 0;
+  }
+  commit_clock();
+  e->stats.events += total;
+  if (!(e->cfg.flags & SDH_FLAG_DEVICE_MATCHES) && e->device_matches > 0) {
+    placed_to_table(e);
+    append_chain(e);
+  }
+}
+
+int do_push_mixed(sdh_engine* e, int32_t n_parts, const sdh_mixed_part* parts, const int32_t* order, int64_t n_order,
+                  int32_t order_on_device) {
+  // ---- refusals, before anything changes ----
+  if (n_parts < 0 || (n_parts > 0 && !parts) || n_order < 0 || (n_order > 0 && !order))
+    throw Error(SDH_E_INVALID, "sdh_engine_push_mixed: bad parts or order");
+  const int ns = (int)e->prog.stream_types.size();
+  std::vector<char> named((size_t)ns, 0);
+  int64_t total = 0;
+  for (int p = 0; p < n_parts; ++p) {
+    const sdh_batch& b = parts[p].batch;
+    const int s = parts[p].stream;
+    if (s < 0 || s >= ns) throw Error(SDH_E_INVALID, fmt("sdh_engine_push_mixed: part %d names stream %d", p, s));
+    if (named[s]) throw Error(SDH_E_INVALID, fmt("sdh_engine_push_mixed: stream %d is named twice", s));
+    named[s] = 1;
+    if (b.chunk) throw Error(SDH_E_INVALID, fmt("sdh_engine_push_mixed: part %d is a chunk (chunk delivery is per stream)", p));
+    const int na = (int)e->prog.stream_types[s].size();
+    if (b.n_cols != na)
+      throw Error(SDH_E_INVALID, fmt("stream %d has %d attributes, part %d has %d", s, na, p, b.n_cols));
+    if (b.n < 0 || (b.n > 0 && (!b.ts || (na > 0 && !b.cols))))
+      throw Error(SDH_E_INVALID, fmt("sdh_engine_push_mixed: part %d has a bad batch", p));
+    if ((b.on_device != 0) != (parts[0].batch.on_device != 0))
+      throw Error(SDH_E_INVALID, "sdh_engine_push_mixed: host and device parts in one call");
+    total += b.n;
+  }
+  if (n_order != total)
+    throw Error(SDH_E_INVALID, fmt("sdh_engine_push_mixed: order has %lld entries, the parts %lld events",
+                                   (long long)n_order, (long long)total));
+  if (e->cfg.max_batch > 0 && total > e->cfg.max_batch) throw Error(SDH_E_INVALID, "batch larger than max_batch");
+  if (total == 0) return SDH_OK;
+  HIPCHK(hipSetDevice(e->dev));
+  const bool native = mix_native_ok(e, n_parts, parts, total);
+  // the parts' counts in `order`: on the host, or for a device order bound for the native path by the
+  // pre-pass's count and scan (nothing of the engine's state is touched by them)
+  std::vector<int32_t> horder;
+  std::vector<int64_t> cnt((size_t)std::max(n_parts, 1), 0);
+  bool counted = false;
+  if (order_on_device && native) {
+    MixPre A{};
+    A.order = order;
+    A.n = total;
+    A.n_parts = n_parts;
+    e->d_mix_cnt.ensure((size_t)sdh_mix_blocks(total) * MIX_MAXP);
+    e->d_mix_total.ensure(MIX_MAXP);
+    e->d_mix_err.ensure(1);
+    A.blk_cnt = e->d_mix_cnt.p;
+    A.total = e->d_mix_total.p;
+    A.err = e->d_mix_err.p;
+    HIPCHK(hipMemsetAsync(e->d_mix_err.p, 0, 4, e->stream));
+    HIPCHK(sdh_mix_count(&A, e->stream));
+    int64_t tot[MIX_MAXP];
+    int32_t bad = 0;
+    HIPCHK(hipMemcpyAsync(tot, e->d_mix_total.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    d2h_sync(e, &bad, e->d_mix_err.p, 4);
+    if (bad) throw Error(SDH_E_INVALID, "sdh_engine_push_mixed: an order entry names no part");
+    for (int p = 0; p < n_parts; ++p) cnt[p] = tot[p];
+    counted = true;
+  } else {
+    const int32_t* ho = order;
+    if (order_on_device) {
+      horder.resize((size_t)total);
+      HIPCHK(hipMemcpy(horder.data(), order, (size_t)total * 4, hipMemcpyDeviceToHost));
+      ho = horder.data();
+    }
+    for (int64_t k = 0; k < total; ++k) {
+      if (ho[k] < 0 || ho[k] >= n_parts) throw Error(SDH_E_INVALID, "sdh_engine_push_mixed: an order entry names no part");
+      ++cnt[ho[k]];
+    }
+  }
+  for (int p = 0; p < n_parts; ++p)
+    if (cnt[p] != parts[p].batch.n)
+      throw Error(SDH_E_INVALID, fmt("sdh_engine_push_mixed: order names part %d %lld times, its batch has %lld events",
+                                     p, (long long)cnt[p], (long long)parts[p].batch.n));
+  if (!native && (e->cfg.flags & SDH_FLAG_DEVICE_MATCHES))
+    throw Error(SDH_E_UNSUPPORTED, "sdh_engine_push_mixed: this call runs as one push per same-stream run, and with "
+                                   "SDH_FLAG_DEVICE_MATCHES each run would drop the records of the run before it");
+  for (int p = 0; p < n_parts; ++p)
+    if (parts[p].batch.n > 0) check_fan_strings(e, parts[p].stream);
+  if (native) {
+    mix_native(e, n_parts, parts, order, total, order_on_device != 0, counted);
+    ++e->mixed_native;
+  } else {
+    mix_split(e, parts, mix_runs(order_on_device ? horder.data() : order, total, n_parts));
+    ++e->mixed_split;
+  }
+  return SDH_OK;
+}
+
 // knobs.h: the knobs of the engine whose ABI call runs on this thread
 thread_local const std::vector<std::pair<std::string, std::string>>* t_knobs = nullptr;
 struct KnobScope {
@@ -1479,6 +1803,15 @@ int sdh_engine_push(sdh_engine* e, int32_t stream, const sdh_batch* b) {
   });
 }
 
+int sdh_engine_push_mixed(sdh_engine* e, int32_t n_parts, const sdh_mixed_part* parts, const int32_t* order,
+                          int64_t n_order, int32_t order_on_device) {
+  if (!e) return SDH_E_INVALID;
+  return guard(e, [&]() {
+    check_usable(e);
+    return do_push_mixed(e, n_parts, parts, order, n_order, order_on_device);
+  });
+}
+
 int sdh_engine_reserve(sdh_engine* e, int64_t bytes) {
   if (!e || bytes < 0) return SDH_E_INVALID;
   return guard(e, [&]() {
@@ -1695,6 +2028,14 @@ int sdh_engine_debug_digest(sdh_engine* e, uint64_t* out) {
 int sdh_engine_debug_shared_pushes(sdh_engine* e, int64_t* out) {
   if (!e || !out) return SDH_E_INVALID;
   *out = e->r_shared_pushes;
+  return SDH_OK;
+}
+
+// Test diagnostic: sdh_engine_push_mixed calls so far run natively / split into run pushes
+int sdh_engine_debug_mixed_pushes(sdh_engine* e, int64_t* out) {
+  if (!e || !out) return SDH_E_INVALID;
+  out[0] = e->mixed_native;
+  out[1] = e->mixed_split;
   return SDH_OK;
 }
 

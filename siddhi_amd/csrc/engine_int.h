@@ -173,6 +173,15 @@ struct sdh_engine {
   DevBuf<InstHeader> d_hdr[2];
   DevBuf<int64_t> d_part[2];
   std::vector<int> cur;              // which buffer holds each local query's state
+  // interleaved pushes (sdh_engine_push_mixed; mixed.hip): `mix` is set while a native
+  // call's K_chain launch runs (launch_once then takes the MIX = true kernels); the pre-pass's outputs,
+  // and the host parts' columns in HBM (one buffer per part: d_batch holds one batch)
+  const MixLaunch* mix = nullptr;
+  DevBuf<MixLaunch> d_mix;
+  DevBuf<int32_t> d_mix_order, d_mix_idx, d_mix_pos, d_mix_cnt, d_mix_pstream, d_mix_err;
+  DevBuf<int64_t> d_mix_ts, d_mix_total;
+  DevBuf<uint8_t> d_mix_batch[MIX_MAXP];
+  int64_t mixed_native = 0, mixed_split = 0;  // calls so far by path (sdh_engine_debug_mixed_pushes)
   // batch staging for host-resident input
   DevBuf<uint8_t> d_batch;           // a host batch's columns in HBM (stage_host_batch)
   HostBuf<uint8_t> stage[2];         // pinned staging slots

@@ -61,8 +61,9 @@ void launch(sdh_engine* e, int stream, const StreamBatch& B, const int64_t t01[2
     // the register forms can only double; the paged form counted what it could not store, so one
     // re-run fits (with an eighth of headroom, and at most 8x: a long push counts partials as lost
     // that would have expired had they been stored)
+    // (an interleaved push runs the paged form at every table size)
     int64_t want = 2 * (int64_t)e->pcap;
-    if (e->chain_paged)
+    if (e->chain_paged || e->mix)
       want = std::min<int64_t>(8 * (int64_t)e->pcap, std::max<int64_t>(want, (int64_t)need + need / 8));
     if (sdh::knob("SDH_TRACE"))
       fprintf(stderr, "[sdh] chain tables %d -> %lld partials per query (needed %d)\n", e->pcap, (long long)want, need);
@@ -98,7 +99,8 @@ int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64
   // the paged form runs the queries that hold partials (two states or more). Each chunk but a query's
   // last works in a scratch table of pcap entries; together they take at most 1 GiB,
   // which bounds the chunks per paged query
-  auto paged = [&](int li) { return e->chain_paged && e->lq[li].cq.n_states >= 2; };
+  // (an interleaved push, e->mix: the MIX = true paged kernels for every query, one-state ones too)
+  auto paged = [&](int li) { return e->mix || (e->chain_paged && e->lq[li].cq.n_states >= 2); };
   int64_t n_paged = 0;
   for (int li : order) n_paged += paged(li) ? 1 : 0;
   const int64_t tbl_bytes = (int64_t)NF * e->pcap * 8;
@@ -152,6 +154,7 @@ int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64
   L.err = e->d_err.p;
   L.scratch = e->d_pscratch.p;
   L.rcode = e->d_rcode.p;
+  L.mix = e->mix;
   const size_t lds = 0;
   HIPCHK(hipEventRecord(e->ev0, e->stream));
   for (int i0 = 0; i0 < n_items;) {
@@ -162,7 +165,8 @@ int32_t launch_once(sdh_engine* e, int stream, const StreamBatch& B, const int64
     Ls.work = e->d_work.p + i0;
     Ls.seg_count = e->d_seg_count.p + i0;
     Ls.n_work = i1 - i0;
-    if (paged(e->work[i0].q)) HIPCHK(sdh_launch_chain_paged(S, e->chain_resid, &Ls, (Ls.n_work + 3) / 4, e->stream));
+    if (e->mix) HIPCHK(sdh_launch_chain_mixed(S, e->chain_resid, &Ls, (Ls.n_work + 3) / 4, e->stream));
+    else if (paged(e->work[i0].q)) HIPCHK(sdh_launch_chain_paged(S, e->chain_resid, &Ls, (Ls.n_work + 3) / 4, e->stream));
     else HIPCHK(sdh_launch_chain(S, e->K, e->chain_resid, &Ls, (Ls.n_work + 3) / 4, lds, e->stream));
     i0 = i1;
   }

@@ -12,6 +12,7 @@
 namespace sdh {
 struct StreamBatch;
 struct ChainLaunch;
+struct MixPre;
 struct RatchetGroup;
 struct RatchetLaunch;
 struct SharedLaunch;
@@ -86,6 +87,15 @@ extern "C" hipError_t sdh_launch_chain(int n_states, int k, int resid, const sdh
                                        size_t lds, hipStream_t s);
 extern "C" hipError_t sdh_launch_chain_paged(int n_states, int resid, const sdh::ChainLaunch* L, int n_blocks,
                                              hipStream_t s);
+// an interleaved push (ChainLaunch::mix): the MIX = true paged kernels; the pre-pass over `order` and
+// the event store's append at merged positions (mixed.hip)
+extern "C" hipError_t sdh_launch_chain_mixed(int n_states, int resid, const sdh::ChainLaunch* L, int n_blocks,
+                                             hipStream_t s);
+extern "C" int64_t sdh_mix_blocks(int64_t n);
+extern "C" hipError_t sdh_mix_count(const sdh::MixPre* A, hipStream_t s);
+extern "C" hipError_t sdh_mix_write(const sdh::MixPre* A, hipStream_t s);
+extern "C" hipError_t sdh_store_append_mixed(const sdh::StreamBatch* B, uint32_t float_mask, const int32_t* pos,
+                                             int64_t first, int64_t* rows, int64_t mask, int W, hipStream_t s);
 extern "C" hipError_t sdh_chain_relayout(const int64_t* src, int64_t* dst, int64_t rows, int old_cap, int new_cap,
                                          hipStream_t s);
 extern "C" hipError_t sdh_launch_ratchet(int key_kind, int xmask, int full, int nf, int sim, int ML, int SC,

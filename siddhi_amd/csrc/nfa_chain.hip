@@ -33,7 +33,8 @@
 // the range it reads (err[1]); the host re-runs the batch unchunked otherwise.
 //
 // Paged form (nfa_chain_paged_kernel; more than 512 partials per query -- 256 in an engine with a
-// residual program, engine_int.h chain_reg_limit -- or SDH_CHAIN_PAGED): the
+// residual program, engine_int.h chain_reg_limit -- or SDH_CHAIN_PAGED, or an interleaved push, whose
+// MIX = true instantiations are described at the kernel): the
 // reference's pending lists are unbounded (StreamPreStateProcessor.java:59-60, :203-216, walked in
 // full at :298) and registers end at 64 * 8 partials, so past that the table stays in HBM, same
 // field-major layout, in pages of 64 entries (one coalesced load per field). The walk is entry-major
@@ -585,9 +586,16 @@ __device__ __forceinline__ int page_store(int64_t* tab, int cap, int64_t at, int
   return __popcll(m);
 }
 
-template <int S, bool R>
+// MIX (an interleaved push, DESIGN.md §3.2 "Interleaved pushes"): the tile's events come from several
+// parts, one stream each. Lane e stages event idx[e] of part order[e]: its columns are loaded from that
+// part alone (the lanes of one part in a tile hold consecutive indices, so each part's loads stay
+// coalesced), a state is examined at event k iff k's part carries the state's stream, and the seed opens
+// at the events of the start state's stream. Which part carries a state's stream is wave-uniform (sp[],
+// SGPRs); which events a state sees is one ballot per state and tile (stm[]). One-state queries run here
+// too under MIX (every passing event is a match; they hold no partials).
+template <int S, bool R, bool MIX>
 __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
-  static_assert(S >= 2, "a one-state chain holds no partials");
+  static_assert(S >= 2 || MIX, "a one-state chain holds no partials");
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int wid = blockIdx.x * 4 + wv;
@@ -600,10 +608,17 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
   const int64_t within = Q->within < 0 ? INT64_MAX : Q->within;
   const int every = Q->every, n_cap = Q->n_cap, qid = Q->qid, n_col = Q->n_col;
   StateDesc D[S];
+  [[maybe_unused]] const MixLaunch* __restrict__ M = L.mix;
+  [[maybe_unused]] int sp[S];  // MIX: the part that carries state s's stream (-1: none of this call)
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     StateDesc d{};
-    d.active = Q->state_stream[s] == stream;
+    if constexpr (MIX) {
+      sp[s] = M->part_of_stream[Q->state_stream[s]];
+      d.active = sp[s] >= 0;
+    } else {
+      d.active = Q->state_stream[s] == stream;
+    }
     d.has_x = Q->xa_count[s] > 0;
     if (d.has_x) {
       const Atom& A = Q->atoms[Q->xa_atom[Q->xa_first[s]]];
@@ -624,7 +639,7 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
     D[s] = d;
   }
 
-  bool any_active = false;  // a non-start state reads this launch's stream
+  bool any_active = false;  // a non-start state reads this launch's stream (MIX: set per tile)
 #pragma unroll
   for (int s = 1; s < S; ++s) any_active = any_active || D[s].active;
 
@@ -653,12 +668,36 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
     const int64_t e = t + lane;
     const bool live = e < W.c1;
     const int64_t ets = live ? L.b.ts[e] : INT64_MAX;
+    [[maybe_unused]] int ep = -1;     // MIX: the event's part and its index within it
+    [[maybe_unused]] int64_t ei = 0;
+    if constexpr (MIX) {
+      if (live) {
+        ep = M->order[e];
+        ei = M->idx[e];
+      }
+    }
     int64_t ck[MAXCOL];
     uint32_t cnul = 0;
 #pragma unroll
     for (int c = 0; c < MAXCOL; ++c) {
       ck[c] = 0;
-      if (c < n_col && Q->col_stream[c] == stream) {
+      if constexpr (MIX) {
+        // the column's part is wave-uniform; only that part's events load it (the others: key 0, not null)
+        const int pc = c < n_col ? M->part_of_stream[Q->col_stream[c]] : -1;
+        if (pc >= 0) {
+          const StreamBatch& Bp = M->parts[pc];
+          const int a = Q->col_attr[c];
+          uint64_t raw = 0;
+          if (ep == pc) {
+            const int wdt = Bp.width[a];
+            if (wdt == 8) raw = ((const uint64_t*)Bp.col[a])[ei];
+            else if (wdt == 4) raw = ((const uint32_t*)Bp.col[a])[ei];
+            else raw = ((const uint8_t*)Bp.col[a])[ei];
+            if (Bp.nul[a] && ((const uint8_t*)Bp.nul[a])[ei]) cnul |= 1u << c;
+          }
+          ck[c] = to_key(raw, Q->col_conv[c]);
+        }
+      } else if (c < n_col && Q->col_stream[c] == stream) {
         const int a = Q->col_attr[c];
         uint64_t raw = 0;
         if (live) {
@@ -679,11 +718,16 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
       return v;
     };
     uint64_t smask[S];
+    [[maybe_unused]] uint64_t stm[S];  // MIX: the tile's events of state s's stream
     int64_t xcur[S];
     uint32_t xnul = 0;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       bool ok = live && D[s].active;
+      if constexpr (MIX) {
+        ok = ok && ep == sp[s];
+        stm[s] = __ballot(ok);
+      }
       xcur[s] = 0;
       if (D[s].active) {
         const int a1 = Q->atom_begin[s + 1] - Q->xa_count[s];
@@ -719,10 +763,18 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
         capn |= ((cnul >> Q->cap_col[c]) & 1u) << c;
       }
     }
-    int64_t pred = __shfl_up(ets, 1, WAVE);
-    if (lane == 0) pred = prev_tile_ts;
-    if (live && ets < pred) unordered = true;
-    prev_tile_ts = __shfl(ets, WAVE - 1, WAVE);
+    if constexpr (MIX) {
+      // (one unchunked item: the timestamp-order flag drives the chunk fallback only. A tile with no
+      // event of a non-start state's stream walks no page)
+      any_active = false;
+#pragma unroll
+      for (int s = 1; s < S; ++s) any_active = any_active || stm[s] != 0;
+    } else {
+      int64_t pred = __shfl_up(ets, 1, WAVE);
+      if (lane == 0) pred = prev_tile_ts;
+      if (live && ets < pred) unordered = true;
+      prev_tile_ts = __shfl(ets, WAVE - 1, WAVE);
+    }
 
     const int cnt = W.c1 <= t ? 0 : (int)((W.c1 - t) < WAVE ? (W.c1 - t) : WAVE);
 
@@ -744,6 +796,9 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
         for (int s = S - 1; s >= 1; --s) {
           const StateDesc& d = D[s];
           if (!d.active) continue;
+          if constexpr (MIX) {
+            if (!((stm[s] >> k) & 1ull)) continue;  // event k is of another stream
+          }
           const bool last = (s == S - 1);
           const bool cpass = (smask[s] >> k) & 1ull;
           const int64_t cur = readlane64(xcur[s], k);
@@ -832,7 +887,22 @@ __global__ __launch_bounds__(256) void nfa_chain_paged_kernel(ChainLaunch L) {
       open &= 0 - open;
       seed_alive = 0;
     }
-    if (open) {
+    if constexpr (S == 1) {
+      // (MIX only) every event the seed passes is a match of its own
+      if (open) {
+        const bool mine = (open >> lane) & 1ull;
+        const int64_t rank = nmatch + wave_mbcnt(open);
+        if (nmatch + __popcll(open) > W.seg_cap) {
+          seg_over = true;
+        } else if (mine) {
+          int64_t* r = seg + rank * RW;
+          r[0] = qid;
+          r[1] = ets;
+          r[2] = L.b.seq_base + e;
+        }
+        nmatch += __popcll(open);
+      }
+    } else if (open) {
       const uint32_t cm0 = D[0].capmask;
       PSet F;
       F.st = -1;
@@ -920,12 +990,16 @@ static hipError_t launch_r(int n_states, int k, const sdh::ChainLaunch* L, int n
   }
 }
 
-template <bool R>
+template <bool R, bool MIX>
 static hipError_t launch_paged_r(int n_states, const sdh::ChainLaunch* L, int n_blocks, hipStream_t s) {
   switch (n_states) {
-    case 2: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<2, R>), dim3(n_blocks), dim3(256), 0, s, *L); break;
-    case 3: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<3, R>), dim3(n_blocks), dim3(256), 0, s, *L); break;
-    case 4: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<4, R>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 1:
+      if constexpr (MIX) hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<1, R, MIX>), dim3(n_blocks), dim3(256), 0, s, *L);
+      else return hipErrorInvalidValue;
+      break;
+    case 2: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<2, R, MIX>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 3: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<3, R, MIX>), dim3(n_blocks), dim3(256), 0, s, *L); break;
+    case 4: hipLaunchKernelGGL((sdh::nfa_chain_paged_kernel<4, R, MIX>), dim3(n_blocks), dim3(256), 0, s, *L); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -945,7 +1019,17 @@ extern "C" hipError_t sdh_launch_chain(int n_states, int k, int resid, const sdh
 extern "C" hipError_t sdh_launch_chain_paged(int n_states, int resid, const sdh::ChainLaunch* L, int n_blocks,
                                              hipStream_t s) {
   if (n_blocks <= 0) return hipSuccess;
-  return resid ? launch_paged_r<true>(n_states, L, n_blocks, s) : launch_paged_r<false>(n_states, L, n_blocks, s);
+  return resid ? launch_paged_r<true, false>(n_states, L, n_blocks, s)
+               : launch_paged_r<false, false>(n_states, L, n_blocks, s);
+}
+
+// an interleaved push (ChainLaunch::mix): the MIX = true paged kernels, chains of one to four states
+extern "C" hipError_t sdh_launch_chain_mixed(int n_states, int resid, const sdh::ChainLaunch* L, int n_blocks,
+                                             hipStream_t s) {
+  if (n_blocks <= 0) return hipSuccess;
+  if (!L->mix) return hipErrorInvalidValue;
+  return resid ? launch_paged_r<true, true>(n_states, L, n_blocks, s)
+               : launch_paged_r<false, true>(n_states, L, n_blocks, s);
 }
 
 // `rows` table rows ([q][field]) of old_cap lanes each -> new_cap lanes each (K_chain table growth)

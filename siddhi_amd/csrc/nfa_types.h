@@ -124,6 +124,38 @@ struct StreamBatch {
   int64_t prev_ts;          // last timestamp of the previous batch of this stream (INT64_MIN: none)
 };
 
+// An interleaved push (sdh_engine_push_mixed, native path): the events of up to MIX_MAXP
+// streams in one merged sequence. Merged event k is event idx[k] of part order[k]; ChainLaunch::b
+// carries the merged timestamps, the merged count and the first seq (its columns are unused). The
+// struct lives in HBM: the MIX = true kernels read it through wave-uniform loads.
+constexpr int MIX_MAXP = 8;
+struct MixLaunch {
+  const int32_t* order;           // [n] part of merged event k
+  const int32_t* idx;             // [n] its index within the part (mix_prepass)
+  const int32_t* part_of_stream;  // [streams] the part that carries the stream, -1: not in this call
+  int32_t n_parts;
+  int32_t pad;
+  StreamBatch parts[MIX_MAXP];    // the parts' columns (ts unused: the merged ts is ChainLaunch::b.ts)
+};
+
+// The pre-pass of an interleaved push (mixed.hip): from order[k] the per-part exclusive scan idx[k],
+// the merged timestamps and the inverse map pos[pos_off[p] + i] = k.
+struct MixPre {
+  const int32_t* order;
+  int64_t n;
+  int32_t n_parts;
+  int32_t pad;
+  const int64_t* ts[MIX_MAXP];    // the parts' timestamp columns
+  int64_t part_n[MIX_MAXP];       // events per part (an index past it is not dereferenced)
+  int64_t pos_off[MIX_MAXP];      // first entry of part p in pos
+  int32_t* blk_cnt;               // [blocks][MIX_MAXP] events of each part per 256-event block, then scanned
+  int64_t* total;                 // [MIX_MAXP] events of each part in order
+  int32_t* err;                   // [0] an order value outside [0, n_parts)
+  int32_t* idx;                   // [n]
+  int64_t* ts_out;                // [n]
+  int32_t* pos;                   // [n]
+};
+
 struct ChainLaunch {
   const ChainQuery* queries;
   const WorkItem* work;
@@ -141,6 +173,7 @@ struct ChainLaunch {
   int64_t* scratch;         // paged form: working tables of the chunks that are not their query's
                             //   last                              [slot][NF][pcap]
   const kg::GInsn* rcode;   // the engine's residual programs (ChainQuery::rt_* / rp_*); the R = true kernels
+  const MixLaunch* mix;     // an interleaved push (the MIX = true kernels), else null
 };
 
 // ------------------------------------------------------------------------------------------

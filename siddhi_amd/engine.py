@@ -71,6 +71,35 @@ class SdhBatch(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("chunk", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class SdhMixedPart(ctypes.Structure):
+    """sdh_mixed_part (include/siddhi_hip.h): one stream's events of an interleaved push."""
+    _fields_ = [("stream", ctypes.c_int32), ("reserved", ctypes.c_int32), ("batch", SdhBatch)]
+
+
+def mixed_runs(counts: Sequence[int], order) -> List[tuple]:
+    """The maximal same-part runs of an interleaved push: [(part, first event of the part, events)],
+    what sdh_engine_push_mixed is defined against (one sdh_engine_push per run). ``counts`` are the parts'
+    event counts; ValueError when ``order`` names no part or does not name part p counts[p] times."""
+    order = np.asarray(order, dtype=np.int64).reshape(-1)
+    n_parts = len(counts)
+    if len(order) and (order.min() < 0 or order.max() >= n_parts):
+        raise ValueError("order names no part")
+    used = [0] * n_parts
+    runs = []
+    if len(order):
+        cut = np.flatnonzero(np.diff(order)) + 1
+        starts = np.concatenate(([0], cut))
+        ends = np.concatenate((cut, [len(order)]))
+        for a, b in zip(starts.tolist(), ends.tolist()):
+            p = int(order[a])
+            runs.append((p, used[p], b - a))
+            used[p] += b - a
+    for p in range(n_parts):
+        if used[p] != int(counts[p]):
+            raise ValueError(f"order names part {p} {used[p]} times, it has {int(counts[p])} events")
+    return runs
+
+
 class SdhMatches(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("query", ctypes.POINTER(ctypes.c_int64)),
                 ("key", ctypes.POINTER(ctypes.c_int64)), ("ts", ctypes.POINTER(ctypes.c_int64)),
@@ -121,7 +150,8 @@ EXPORTS = ["sdh_engine_create", "sdh_engine_push", "sdh_engine_flush", "sdh_engi
            "sdh_comm_destroy", "sdh_comm_last_error", "sdh_engine_set_comm", "sdh_engine_push_bcast",
            "sdh_engine_gather", "sdh_engine_reserve", "sdh_engine_reserve_keys", "sdh_engine_poll_records",
            "sdh_engine_records_compact", "sdh_engine_debug_shared_pushes", "sdh_engine_retain_events",
-           "sdh_engine_poll_rows", "sdh_engine_query_outputs"]
+           "sdh_engine_poll_rows", "sdh_engine_query_outputs", "sdh_engine_push_mixed",
+           "sdh_engine_debug_mixed_pushes"]
 SDH_COMM_ID_BYTES = 128
 
 _lib = None
@@ -186,6 +216,10 @@ def load_library(path: str = LIB_PATH):
         lib.sdh_engine_poll_rows.argtypes = [P, ctypes.c_int32, ctypes.POINTER(SdhRows)]
         lib.sdh_engine_query_outputs.argtypes = [P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
+    if hasattr(lib, "sdh_engine_push_mixed"):  # (as above: an older build lacks it)
+        lib.sdh_engine_push_mixed.argtypes = [P, ctypes.c_int32, ctypes.POINTER(SdhMixedPart), P, ctypes.c_int64,
+                                              ctypes.c_int32]
+        lib.sdh_engine_debug_mixed_pushes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
     _lib = lib
     return lib
 
@@ -280,6 +314,57 @@ class HipEngine:
         cp = (ctypes.c_void_p * len(col_ptrs))(*col_ptrs)
         b = SdhBatch(n=n, ts=ts_ptr, cols=cp, nulls=None, n_cols=len(col_ptrs), on_device=1, chunk=int(chunk))
         self._check(self.lib.sdh_engine_push(self.h, stream, ctypes.byref(b)))
+
+    def push_mixed_columns(self, parts, order):
+        """Interleaved push of host columns (sdh_engine_push_mixed): ``parts`` is a sequence of
+        (stream, ts, cols, nulls or None), ``order[k]`` the part of the call's k-th event."""
+        keep, arr = [], (SdhMixedPart * max(1, len(parts)))()
+        for i, (stream, ts, cols, nulls) in enumerate(parts):
+            ts = np.ascontiguousarray(ts, dtype=np.int64)
+            cp = (ctypes.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
+            nptr = None
+            keep += [ts, cp] + list(cols)
+            if nulls is not None:
+                nl = [None if x is None else np.ascontiguousarray(x, dtype=np.uint8) for x in nulls]
+                nptr = (ctypes.c_void_p * max(1, len(cols)))(*[0 if x is None else x.ctypes.data for x in nl])
+                keep += [nptr] + [x for x in nl if x is not None]
+            arr[i].stream = stream
+            arr[i].batch = SdhBatch(n=len(ts), ts=ts.ctypes.data, cols=cp, nulls=nptr, n_cols=len(cols), on_device=0,
+                                    chunk=0)
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        self._check(self.lib.sdh_engine_push_mixed(self.h, len(parts), arr, order.ctypes.data, len(order), 0))
+        del keep
+
+    def push_mixed_device(self, parts, order_ptr: int, n_order: int, order_on_device: bool = True):
+        """Interleaved push of parts resident in HBM: ``parts`` is a sequence of (stream, n, ts_ptr, col_ptrs);
+        ``order_ptr`` an int32 array of n_order entries, in HBM (or on the host: order_on_device False)."""
+        keep, arr = [], (SdhMixedPart * max(1, len(parts)))()
+        for i, (stream, n, ts_ptr, col_ptrs) in enumerate(parts):
+            cp = (ctypes.c_void_p * max(1, len(col_ptrs)))(*col_ptrs)
+            keep.append(cp)
+            arr[i].stream = stream
+            arr[i].batch = SdhBatch(n=n, ts=ts_ptr, cols=cp, nulls=None, n_cols=len(col_ptrs), on_device=1, chunk=0)
+        self._check(self.lib.sdh_engine_push_mixed(self.h, len(parts), arr, order_ptr, int(n_order),
+                                                   int(bool(order_on_device))))
+        del keep
+
+    def send_mixed(self, parts, order):
+        """tests/harness.App-style interleaved send: parts as (stream, ts, vals, nulls), raw 64-bit words."""
+        out = []
+        for stream, ts, vals, nulls in parts:
+            types = self.stream_types[stream]
+            cols = columns_from_words(np.asarray(vals, dtype=np.int64).reshape(len(ts), len(types)), types)
+            nl = None
+            if nulls is not None and np.any(nulls):
+                nl = [np.ascontiguousarray(nulls[:, j]) for j in range(len(types))]
+            out.append((stream, np.asarray(ts, dtype=np.int64), cols, nl))
+        self.push_mixed_columns(out, order)
+
+    def debug_mixed_pushes(self):
+        """(native, split): the push_mixed calls so far by path (sdh_engine_debug_mixed_pushes)."""
+        out = (ctypes.c_int64 * 2)()
+        self._check(self.lib.sdh_engine_debug_mixed_pushes(self.h, out))
+        return int(out[0]), int(out[1])
 
     # interface used by tests/harness.App -------------------------------------------------------
     def send(self, stream: int, ts, vals: np.ndarray, nulls: Optional[np.ndarray], as_chunk=False):
