@@ -235,13 +235,17 @@ int sdh_engine_push(sdh_engine* e, int32_t stream, const sdh_batch* batch);
  * count that is not its stream's, mixed on_device among the parts, n_order != the sum of the parts' n, a
  * part whose count in `order` is not its n (or an order value outside [0, n_parts)), a total above
  * max_batch.
- * Two paths (DESIGN.md §3.2 "Interleaved pushes"). Native: one K_chain launch over the merged sequence,
- * taken when every query that reads a named stream is a K_chain query (no K_ratchet / K_gate group and
- * no K_gen-family or K_wave set reads one), no communicator is set, and at most 8 parts are named.
- * Otherwise the engine itself splits the call into its runs and pushes each. With SDH_FLAG_DEVICE_MATCHES
- * a run push would drop the records of the run before it, so there a call that cannot run natively
- * fails with SDH_E_UNSUPPORTED, nothing changed; a native call's device records are one segment set,
- * as after sdh_engine_push. */
+ * Two paths (DESIGN.md §3.2 "Interleaved pushes"). Native: one K_chain launch and / or one K_gen launch
+ * over the merged sequence, taken when every query that reads a named stream is a K_chain query or an
+ * unpartitioned query run by the K_gen kernel (logical states, counts over another stream, `every` inside
+ * a chain, ...), no K_gen set of the engine has absent states, no communicator is set, at most 8 parts
+ * are named, and the journal of the K_gen blocks the call modifies fits its budget (a third of free
+ * device memory). A named stream read by a K_ratchet / K_gate group, a K_seq group, a K_wave, K_part or
+ * K_slab set or a partition's K_gen set keeps the call off it. Otherwise the engine itself splits the
+ * call into its runs and pushes each. With SDH_FLAG_DEVICE_MATCHES a run push would drop the records of
+ * the run before it, so there every call that cannot run natively fails with SDH_E_UNSUPPORTED, nothing
+ * changed; a native call's device records (K_chain segments and K_gen flat records) are handed out
+ * together by sdh_engine_poll_records, as after an sdh_engine_push that both plans read. */
 typedef struct sdh_mixed_part {
   int32_t stream;
   int32_t reserved;          /* 0 */
@@ -532,8 +536,8 @@ int sdh_engine_debug_digest(sdh_engine* e, uint64_t* out);
 /* Test diagnostic: *out = the pushes so far whose K_ratchet records were written by the shared-pops
  * form (the pops computed once per push; SDH_RATCHET_SHARED_MIN / SDH_RATCHET_NO_SHARED in debug). */
 int sdh_engine_debug_shared_pushes(sdh_engine* e, int64_t* out);
-/* Test diagnostic: out[0] = the sdh_engine_push_mixed calls so far that ran natively (one K_chain launch
- * over the merged sequence), out[1] = those the engine split into run pushes (SDH_MIX_SPLIT=1 in debug
+/* Test diagnostic: out[0] = the sdh_engine_push_mixed calls so far that ran natively (one K_chain and /
+ * or K_gen launch over the merged sequence), out[1] = those the engine split into run pushes (SDH_MIX_SPLIT=1 in debug
  * forces that path). No-op calls (n_order == 0) and refused calls count in neither. */
 int sdh_engine_debug_mixed_pushes(sdh_engine* e, int64_t* out /* 2 entries */);
 /* Diagnostic: best-of-`iters` HBM bandwidth of a streaming copy (bytes read + written) and a

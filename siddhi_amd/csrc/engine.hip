@@ -10,6 +10,7 @@
 // batched launch per pushed event batch.
 #include "engine_int.h"
 #include "launchers.h"
+#include "mix_plan.h"
 
 namespace {
 
@@ -700,24 +701,39 @@ void mix_split(sdh_engine* e, const sdh_mixed_part* parts, const std::vector<Mix
   }
 }
 
-// every consumer of the named streams is a K_chain query, and nothing else stands in the way
-bool mix_native_ok(const sdh_engine* e, int n_parts, const sdh_mixed_part* parts, int64_t total) {
+// the call as mix_plan.h sees it: per named stream the plans that read it, and the engine-wide facts.
+// *gen_runs: a K_gen query reads a part that has events (the native call launches the K_gen kernel)
+mixplan::Call mix_call(const sdh_engine* e, int n_parts, const sdh_mixed_part* parts, int64_t total, bool* gen_runs) {
+  static_assert(mixplan::MAX_PARTS == MIX_MAXP, "part limit");
+  mixplan::Call c;
   const char* k = sdh::knob("SDH_MIX_SPLIT");
-  if ((k && atoi(k) != 0) || e->comm || n_parts > MIX_MAXP || total >= INT32_MAX) return false;
-  for (const auto& gs : e->gsets)
-    if (gs->timed) return false;  // absent states: time passes for the set on every push, whatever its stream
-  for (int p = 0; p < n_parts; ++p) {
+  c.knob_split = k && atoi(k) != 0;
+  c.comm = e->comm != nullptr;
+  c.n_parts = n_parts;
+  c.total = total;
+  for (const auto& gs : e->gsets) c.timed_gen |= gs->timed;  // time passes for the set on every push, whatever its stream
+  *gen_runs = false;
+  for (int p = 0; p < n_parts && p < MIX_MAXP; ++p) {
     const int s = parts[p].stream;
+    uint32_t kinds = 0;
+    for (const auto& q : e->lq)
+      if (std::find(q.streams.begin(), q.streams.end(), s) != q.streams.end()) kinds |= mixplan::C_CHAIN;
     for (const auto& g : e->rg)
-      if (g.stream == s) return false;  // K_ratchet / K_gate
-    for (const auto& g : e->gq)         // the K_gen family, K_wave included
-      if (s >= kg::GMAXSTREAM || g.recv_n[s] > 0) return false;
+      if (g.stream == s) kinds |= g.n_g > 0 ? mixplan::C_GATE : mixplan::C_RATCHET;
+    if (s >= kg::GMAXSTREAM) {
+      if (!e->gq.empty()) kinds |= mixplan::C_RANGE;
+    } else {
+      for (size_t i = 0; i < e->gq.size(); ++i)
+        if (e->gq[i].recv_n[s] > 0) kinds |= e->gq_kind[i];
+    }
+    c.consumers[p] = kinds;
+    if ((kinds & mixplan::C_GEN) && parts[p].batch.n > 0) *gen_runs = true;
   }
-  return true;
+  return c;
 }
 
-// the native path: pre-pass, one K_chain launch over the merged sequence, the table append and the
-// event store from the merged positions. cnt: the parts' events; order: host or device (order_dev)
+// the native path: pre-pass, one K_chain launch and one K_gen launch over the merged sequence, the table
+// append and the event store from the merged positions. cnt: the parts' events; order: host or device (order_dev)
 void mix_native(sdh_engine* e, int n_parts, const sdh_mixed_part* parts, const int32_t* order, int64_t total,
                 bool order_dev, bool counted) {
   const bool on_dev = parts[0].batch.on_device != 0;
@@ -837,6 +853,18 @@ void mix_native(sdh_engine* e, int n_parts, const sdh_mixed_part* parts, const i
     }
     if (reads) qs.push_back(li);
   }
+  // the K_gen queries likewise (all of them in the unpartitioned set: mix_plan.h), per part they read
+  uint32_t gen_mask = 0;
+  for (int p = 0; p < n_parts; ++p) {
+    const int s = parts[p].stream;
+    if (parts[p].batch.n == 0 || s >= kg::GMAXSTREAM) continue;
+    for (const auto& g : e->gq)
+      if (g.recv_n[s] > 0) {
+        gen_mask |= 1u << s;
+        pe += parts[p].batch.n;
+        ++consumers;
+      }
+  }
   if (!e->started) {
     e->started = true;
     e->start_ts = t01[0];
@@ -857,6 +885,7 @@ void mix_native(sdh_engine* e, int n_parts, const sdh_mixed_part* parts, const i
   e->dev_polled = false;
   e->last_n = total;
   e->last_seq_base = B.seq_base;
+  for (auto& k : e->part_kept) k = total;
   e->stats.last_gen_items = 0;
   e->stats.last_seq_items = 0;
   auto commit_clock = [&]() {
@@ -864,30 +893,50 @@ void mix_native(sdh_engine* e, int n_parts, const sdh_mixed_part* parts, const i
       if (parts[p].batch.n > 0) e->prev_ts[parts[p].stream] = last_ts[p];
     e->seq += total;
   };
-  if (!qs.empty()) {
+  double ms = 0, bytes = 0;
+  if (!qs.empty() || gen_mask) {
     e->mix = e->d_mix.p;
+    e->mix_mask = gen_mask;
     try {
-      bool unordered = false;
-      launch(e, -1, B, t01, qs, false, &unordered);
+      if (!qs.empty()) {
+        bool unordered = false;
+        launch(e, -1, B, t01, qs, false, &unordered);
+        for (int li : qs) e->cur[li] ^= 1;
+        ms = e->stats.last_kernel_ms;
+        bytes = e->stats.last_kernel_bytes;
+      }
+      // the K_gen pass after the K_chain launch, with launch_gen's own journal and exact re-runs: a pool or
+      // output overflow repeats this pass alone (the K_chain launch above has its own loop)
+      if (gen_mask) {
+        double gms = 0, gbytes = 0;
+        launch_gen(e, -1, B, &gms, &gbytes);  // (adds its records to stats.matches)
+        ms += gms;
+        bytes += gbytes;
+      }
     } catch (const std::exception& ex) {
       e->mix = nullptr;
+      e->mix_mask = 0;
       commit_clock();
       e->broken = ex.what();
       throw;
     }
     e->mix = nullptr;
-    for (int li : qs) e->cur[li] ^= 1;
+    e->mix_mask = 0;
   }
   if (consumers) {
     e->stats.pattern_events += pe;
     e->stats.matches += e->device_matches;
-    if (qs.empty()) e->stats.last_kernel_ms = e->stats.last_kernel_bytes = 0;
+    e->stats.last_kernel_ms = ms;
+    e->stats.last_kernel_bytes = bytes;
   }
   commit_clock();
   e->stats.events += total;
-  if (!(e->cfg.flags & SDH_FLAG_DEVICE_MATCHES) && e->device_matches > 0) {
+  if (!(e->cfg.flags & SDH_FLAG_DEVICE_MATCHES) && (e->device_matches > 0 || e->g_dev_matches > 0)) {
     placed_to_table(e);
     append_chain(e);
+    // bstream (the rank column of narrow records) is unused here: no narrow record kind can occur, the
+    // path writes K_gen's wide records only, which carry their trigger's stream in word 6
+    append_gen(e, B.ts, B.seq_base, 0);
   }
 }
 
@@ -921,7 +970,18 @@ int do_push_mixed(sdh_engine* e, int32_t n_parts, const sdh_mixed_part* parts, c
   if (e->cfg.max_batch > 0 && total > e->cfg.max_batch) throw Error(SDH_E_INVALID, "batch larger than max_batch");
   if (total == 0) return SDH_OK;
   HIPCHK(hipSetDevice(e->dev));
-  const bool native = mix_native_ok(e, n_parts, parts, total);
+  bool gen_runs = false;
+  bool native = mixplan::why_split(mix_call(e, n_parts, parts, total, &gen_runs)) == nullptr;
+  // the K_gen pass journals the blocks it modifies (gen_journal): a call whose bound does not fit the
+  // budget is not native -- decided here, before anything changes. (The split path's run pushes halve
+  // their batches as do_push does.)
+  if (native && gen_runs) {
+    size_t fr = 0, tot = 0;
+    const char* jb = sdh::knob("SDH_JOURNAL_BUDGET");
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess && gen_journal_bound(e, total) > (jb ? atof(jb) : (double)fr / 3))
+      native = false;
+    (void)hipGetLastError();
+  }
   // the parts' counts in `order`: on the host, or for a device order bound for the native path by the
   // pre-pass's count and scan (nothing of the engine's state is touched by them)
   std::vector<int32_t> horder;

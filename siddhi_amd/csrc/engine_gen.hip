@@ -5,6 +5,7 @@
 #include "launchers.h"
 #include "chm_order.h"
 #include "java_fmt.h"
+#include "mix_plan.h"
 #include "part_lower.h"
 #include "slab_lower.h"
 #include "spec.h"
@@ -321,6 +322,20 @@ void gen_build(sdh_engine* e, const std::vector<int>& qis) {
     std::sort(m.begin(), m.end());
     add_set(pi, m);
   }
+  // which plan runs each query (what an interleaved push's eligibility asks, mix_plan.h)
+  e->gq_kind.assign(e->gq.size(), 0);
+  auto kind_groups = [&](int group_base, int n_groups, uint32_t kind, uint32_t seq_kind) {
+    for (int g = group_base; g < group_base + n_groups; ++g)
+      for (int l = 0; l < 64; ++l)
+        if (e->lane_q[(size_t)g * 64 + l] >= 0) e->gq_kind[e->lane_q[(size_t)g * 64 + l]] = e->group_seq[g] > 0 ? seq_kind : kind;
+  };
+  for (const auto& gs : e->gsets)
+    kind_groups(gs->group_base, gs->n_groups, gs->partition < 0 ? mixplan::C_GEN : mixplan::C_GEN_PART,
+                gs->partition < 0 ? mixplan::C_SEQ : mixplan::C_GEN_PART);
+  for (const auto& ps : e->psets) kind_groups(ps->group_base, ps->n_groups, mixplan::C_PART, mixplan::C_PART);
+  for (const auto& ss : e->ssets) kind_groups(ss->group_base, ss->n_groups, mixplan::C_SLAB, mixplan::C_SLAB);
+  for (const auto& ws : e->wsets)
+    for (int gx : ws->qs) e->gq_kind[gx] = mixplan::C_WAVE;
   e->d_gq.ensure(e->gq.size());
   HIPCHK(hipMemcpy(e->d_gq.p, e->gq.data(), e->gq.size() * sizeof(kg::GQuery), hipMemcpyHostToDevice));
   // the groups' lane-constant table (kg::LaneConsts): [group][slot][64], slot 0 query id, 1 within,
@@ -776,10 +791,59 @@ void gen_chunked(Pass& p, sdh_engine::GenSet& gs, const int32_t* glist, const st
   p.bytes += (double)n * p.ev_bytes * gen_groups.size();  // every group streams the batch once
 }
 
+// an interleaved push (e->mix): one K_gen launch over the merged batch, one item per
+// group whose shape reads a stream of the call (e->mix_mask). No event chunks: kg::seq_lookback needs
+// one input stream. The list depends on the call's streams only: cached by their mask
+void unpartitioned_mixed(Pass& p, sdh_engine::GenSet& gs) {
+  sdh_engine* e = p.e;
+  std::vector<int32_t> gen_groups;
+  int na = 1;
+  for (int g = 0; g < gs.n_groups; ++g) {
+    const kg::GQuery& tq = e->gq[e->group_tmpl[gs.group_base + g]];
+    bool reads = false;
+    for (int s = 0; s < kg::GMAXSTREAM; ++s)
+      if ((e->mix_mask >> s & 1) && tq.recv_n[s] > 0) {
+        reads = true;
+        na = std::max<int>(na, tq.n_cap[s]);
+      }
+    // (a K_seq group that reads a named stream keeps the call off this path: mix_plan.h)
+    if (reads && e->group_seq[gs.group_base + g] == 0) gen_groups.push_back(g);
+  }
+  if (gen_groups.empty()) return;
+  auto& gl = gs.mix_glists[e->mix_mask];
+  if (!gl.p) {
+    gl.ensure(gen_groups.size());
+    HIPCHK(hipMemcpy(gl.p, gen_groups.data(), gen_groups.size() * 4, hipMemcpyHostToDevice));
+  }
+  sdh::GenLaunch L = gen_launch_of(p, gs);
+  L.glist = gl.p;
+  L.n_glist = (int32_t)gen_groups.size();
+  L.n_items = L.n_glist;
+  L.ev_chunks = 1;
+  L.chunk_len = p.B.n;
+  L.no_timers = 1;  // (no set of a native call has absent states)
+  L.mix = e->mix;
+  L.mix_na = na;
+  L.mix_tile = 64;
+  // (measurements: a tile of one event is the unstaged walk, two dependent loads ahead of every event)
+  if (const char* v = sdh::knob("SDH_MIX_GEN_TILE")) {
+    int t = 1;
+    while (2 * t <= std::min(64, std::max(1, atoi(v)))) t *= 2;
+    L.mix_tile = t;
+  }
+  gen_journal(e, gs, 0, L.glist, nullptr, (int64_t)gen_groups.size());
+  HIPCHK(sdh_launch_gen(&L, e->stream));
+  e->stats.last_gen_items += L.n_items;
+  p.any = true;
+  // every group reads order / idx / ts and a captured word or two per event
+  p.bytes += (double)p.B.n * (16 + 8.0 * na) * gen_groups.size();
+}
+
 // an unpartitioned set: of its groups reading this stream, windowed sequences go to K_seq, the rest
 // to K_gen
 void unpartitioned_pass(Pass& p, sdh_engine::GenSet& gs) {
   sdh_engine* e = p.e;
+  if (e->mix) return unpartitioned_mixed(p, gs);
   const int64_t n = p.B.n;
   std::vector<int32_t> seq_rows, gen_groups;
   for (int g = 0; g < gs.n_groups; ++g) {
@@ -1154,9 +1218,10 @@ bool gen_pass(sdh_engine* e, int stream, const StreamBatch& B, bool write, doubl
   for (auto& gs : e->gsets)
     if (gs->partition < 0) unpartitioned_pass(p, *gs);
   e->wave_items = 0;
-  wave_sets(p);
+  // (an interleaved push: no K_wave set and no partition reads a stream of the call, mix_plan.h)
+  if (!e->mix) wave_sets(p);
   e->stats.last_gen_items += e->wave_items;  // (K_wave's items, a wave each, count with K_gen's)
-  for (int pi = 0; pi < (int)e->routes.size(); ++pi)
+  for (int pi = 0; pi < (int)e->routes.size() && !e->mix; ++pi)
     if (e->routes[pi]) partition_pass(p, pi);
   if (p.tail_new_len >= 0) *tail_new_len = p.tail_new_len;
   *bytes_out = p.bytes;

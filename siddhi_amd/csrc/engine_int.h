@@ -174,9 +174,12 @@ struct sdh_engine {
   DevBuf<int64_t> d_part[2];
   std::vector<int> cur;              // which buffer holds each local query's state
   // interleaved pushes (sdh_engine_push_mixed; mixed.hip): `mix` is set while a native
-  // call's K_chain launch runs (launch_once then takes the MIX = true kernels); the pre-pass's outputs,
-  // and the host parts' columns in HBM (one buffer per part: d_batch holds one batch)
+  // call's launches run (launch_once then takes the MIX = true K_chain kernels, gen_pass the mixed walk
+  // of nfa_gen_kernel over the unpartitioned groups that read a stream of mix_mask: the named streams
+  // with events in the call); the pre-pass's outputs, and the host parts' columns in HBM (one buffer per
+  // part: d_batch holds one batch)
   const MixLaunch* mix = nullptr;
+  uint32_t mix_mask = 0;
   DevBuf<MixLaunch> d_mix;
   DevBuf<int32_t> d_mix_order, d_mix_idx, d_mix_pos, d_mix_cnt, d_mix_pstream, d_mix_err;
   DevBuf<int64_t> d_mix_ts, d_mix_total;
@@ -283,6 +286,7 @@ struct sdh_engine {
   DevBuf<int32_t> d_fan_rank;        // [query][stream] its rank within the partition (fan-out), -1
   int64_t advance_to = INT64_MIN;    // set while a time advance runs (sdh_engine_advance_time)
   std::vector<char> gq_arena;        // [gq] the query runs on K_gen (has an instance arena)
+  std::vector<uint32_t> gq_kind;     // [gq] the plan that runs the query, as a mixplan::Consumer bit (mix_plan.h)
   int64_t gen_regrows = 0;           // pool growths so far (sdh_stats)
   struct GenSet {
     int partition = -1;              // -1: the unpartitioned K_gen queries
@@ -297,6 +301,8 @@ struct sdh_engine {
     DevBuf<int32_t> j32;
     DevBuf<int64_t> j64, jidx;
     int64_t jn = 0;
+    // interleaved pushes: the K_gen groups that read a stream of the call, cached by the call's mix_mask
+    std::map<uint32_t, DevBuf<int32_t>> mix_glists;
   };
   std::vector<std::unique_ptr<GenSet>> gsets;
   // per partition: PartitionRuntime's key -> instance map (dense key ids), shared by the

@@ -26,7 +26,14 @@ using dev::gpick;
 using dev::LaneOut;
 using dev::raw_word;
 
-template <int WPE>
+// MIX (an interleaved push, DESIGN.md §3.2 "Interleaved pushes"): the wave walks the merged sequence of
+// several streams' events -- another way of choosing (event, stream, captured words) ahead of the same
+// body. Per tile of L.mix_tile merged events the wave's lanes stage, one event each, the event's
+// stream, null bits, merged timestamp and the words the group's shape captures from that stream into
+// LDS (the two dependent loads order[k] / idx[k] -> the part's column are paid once per tile, and lanes
+// of one part hold consecutive indices); the walk then reads them by broadcast. An event whose stream
+// the shape does not read is skipped on a scalar test, as a run push would not have launched the group.
+template <int WPE, bool MIX>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void nfa_gen_kernel(GenLaunch L) {
   const int lane = threadIdx.x;
   const int item = (int)dev::grid_item(L.xcd);
@@ -53,8 +60,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   const kg::GQuery* __restrict__ q = L.tab.queries + L.tab.group_tmpl[L.group_base + g];
   const kg::GQuery* __restrict__ ql = L.tab.queries + qi;
   // a query that does not read the stream still sees time pass if it has absent states
-  const bool reads = q->recv_n[L.b.stream] != 0;
-  if (!reads && q->lay.TQ == 0) return;
+  // (MIX: the host lists only groups that read a stream of the call; decided per event)
+  bool reads = true;
+  if constexpr (!MIX) {
+    reads = q->recv_n[L.b.stream] != 0;
+    if (!reads && q->lay.TQ == 0) return;
+  }
   int64_t block = L.block_base + (int64_t)kid * L.groups + g;
   int32_t* a32 = L.a32;
   int64_t* a64 = L.a64;
@@ -93,7 +104,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   c.capk = 0;
   c.npin = 0;
   c.n_ret = 0;
-  c.stream = L.b.stream;
+  c.stream = MIX ? 0 : L.b.stream;
+  // MIX: the staged tile after the hot words, [ts[T], stream | null bits << 8 [T], words[T][mix_na]]
+  [[maybe_unused]] int64_t* const stg =
+      (int64_t*)((int32_t*)(gen_lds + kg::GMAXNA + (1 + L.hot_nu) * 64) + (3 * L.hot_s + 4) * 64);
+  [[maybe_unused]] const MixLaunch* __restrict__ const M = L.mix;
   const int64_t key = L.keys.key_of_id ? L.keys.key_of_id[kid] : -1;
   // PartitionRuntime.cloneIfNotExist / QueryRuntime.init: seed (a sweep seeds a clone at its key's
   // first event); only top-level runtimes are start()ed (SiddhiAppRuntime.start)
@@ -105,7 +120,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
   if (!L.sweep && c.i32(q->lay.o_init) == 0) seed();
   LaneOut o = dev::lane_out(L.sink);
   const int S = q->n_states;
-  const int ncap = q->n_cap[c.stream];
+  const int ncap = MIX ? 0 : q->n_cap[c.stream];
   unsigned long long nrec = 0;
   int64_t idx = 0;
   const int64_t fpos = L.fan_pos ? (int64_t)L.fan_pos[kid] << 32 : 0;
@@ -193,17 +208,61 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
       own = !L.sweep || L.fan_pos || (L.ev_kid && L.ev_kid[e] == kid);
     }
     c.seq = L.b.seq_base + e;
-    c.ts = L.b.ts[e];
+    [[maybe_unused]] int64_t meta = 0;
+    [[maybe_unused]] int st = 0;  // MIX: the event's slot in the staged tile
+    if constexpr (MIX) {
+      const int T = L.mix_tile, na = L.mix_na;
+      st = (int)(e & (T - 1));
+      if (st == 0) {  // the lanes still walking share the tile's events among them
+        __syncthreads();  // (one wave: the reads of the tile before are done)
+        const uint64_t act = __ballot(1);
+        const int nact = __popcll(act), rank = (int)__mbcnt_hi((uint32_t)(act >> 32), __mbcnt_lo((uint32_t)act, 0));
+        for (int t = rank; t < T && e + t < e1; t += nact) {
+          const int64_t m = e + t;
+          const StreamBatch* __restrict__ pb = &M->parts[M->order[m]];
+          const int64_t i = M->idx[m];
+          const int sm = pb->stream;
+          int64_t nulls = 0;
+          if (q->recv_n[sm] != 0) {
+            const int nc = q->n_cap[sm];
+            for (int jj = 0; jj < nc; ++jj) {
+              const int a = q->cap_attr[sm][jj];
+              const void* col = pb->col[a];
+              const uint8_t* nl = pb->nul[a];
+              const int w = pb->width[a];
+              stg[2 * T + t * na + jj] = w == 8   ? ((const int64_t*)col)[i]
+                                         : w == 4 ? (int64_t)((const int32_t*)col)[i]
+                                                  : (int64_t)((const uint8_t*)col)[i];
+              if (nl && nl[i]) nulls |= 1ll << jj;
+            }
+          }
+          stg[t] = L.b.ts[m];
+          stg[T + t] = sm | nulls << 8;
+        }
+        __syncthreads();
+      }
+      meta = stg[T + st];
+      c.stream = __builtin_amdgcn_readfirstlane((int)(meta & 0xff));  // the same event for every lane
+      reads = q->recv_n[c.stream] != 0;
+      c.ts = stg[st];
+    } else {
+      c.ts = L.b.ts[e];
+    }
     idx = 0;
     if (inited && timers) c.fire_timers(c.ts, L.playback != 0, emit);  // timers due by this event fire before it
     if (!own) continue;
     if (!inited) seed();
     if (!reads) continue;
-    c.ev_null = 0;
-    for (int jj = 0; jj < ncap; ++jj) {  // the event is the same for every lane: identical LDS stores
-      bool nl;
-      evv[jj] = raw_word(L.b, q->cap_attr[c.stream][jj], e, nl);
-      if (nl) c.ev_null |= 1u << jj;
+    if constexpr (MIX) {  // the staged words, read by broadcast
+      c.ev_null = (uint32_t)(meta >> 8);
+      c.ev_val = stg + 2 * L.mix_tile + st * L.mix_na;
+    } else {
+      c.ev_null = 0;
+      for (int jj = 0; jj < ncap; ++jj) {  // the event is the same for every lane: identical LDS stores
+        bool nl;
+        evv[jj] = raw_word(L.b, q->cap_attr[c.stream][jj], e, nl);
+        if (nl) c.ev_null |= 1u << jj;
+      }
     }
     c.receive(emit);
   }
@@ -551,7 +610,19 @@ extern "C" hipError_t sdh_launch_gen(const sdh::GenLaunch* L, hipStream_t s) {
   // 4 waves/SIMD (116 VGPRs, no spills): on C3, 5 (96 VGPRs + spills) is level and 6 / 8 are
   // 10-30 % slower
   const size_t lds = (size_t)(sdh::kg::GMAXNA + (1 + L->hot_nu) * 64) * 8 + (size_t)(3 * L->hot_s + 4) * 64 * 4;
-  hipLaunchKernelGGL(sdh::nfa_gen_kernel<4>, dim3(L->xcd ? (L->n_items + 7) & ~7 : L->n_items), dim3(64), lds, s, *L);
+  const dim3 grid(L->xcd ? (L->n_items + 7) & ~7 : L->n_items);
+  if (L->mix) {
+    // the mixed walk is plain mode only, and its tile indexing needs a power of two
+    const int T = L->mix_tile;
+    if (L->sweep || L->keys.seg_begin || L->keys.ev_idx || L->ev_chunks > 1 || T < 1 || T > 64 || (T & (T - 1)) ||
+        L->mix_na < 1 || L->mix_na > sdh::kg::GMAXNA)
+      return hipErrorInvalidValue;
+    // the staged tile: at 64 events and one captured word 1.5 KB beside the 8 KB of hot words
+    const size_t stage = (size_t)T * (2 + L->mix_na) * 8;
+    hipLaunchKernelGGL((sdh::nfa_gen_kernel<4, true>), grid, dim3(64), lds + stage, s, *L);
+  } else {
+    hipLaunchKernelGGL((sdh::nfa_gen_kernel<4, false>), grid, dim3(64), lds, s, *L);
+  }
   return hipGetLastError();
 }
 

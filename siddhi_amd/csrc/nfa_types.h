@@ -428,6 +428,13 @@ struct GenLaunch {
   // match record's idx word carries the key's position in the reference's junction map
   // (chm_order.h) above the emission index: fan_pos[kid] << 32 | idx
   const int32_t* fan_pos;
+  // an interleaved push (the MIX = true kernel; plain mode only: no sweep, no key segments, no event
+  // chunks): b carries the merged timestamps, count and first seq; merged event k is event mix->idx[k]
+  // of part mix->order[k], and the wave stages mix_tile events at a time (a power of two up to 64) with
+  // mix_na captured words each (the widest n_cap of the launch's shapes over the call's streams)
+  const MixLaunch* mix;
+  int32_t mix_na;
+  int32_t mix_tile;
 };
 
 // ------------------------------------------------------------------------------------------

@@ -16,6 +16,18 @@ whether it belongs to A or B. Each call carries --events merged events, parts an
                                                      pushes through sdh_engine_push cost; match table mode,
                                                      device records do not survive a run push)
 
+    python tools/mixed_bench.py --plan gen           the same legs over the cross-stream logical family
+
+        every e1=A[price > T_p] -> e2=B[price > e1.price] and e3=A[price > T_p + 2] within W_p milliseconds
+
+                                                     (W_p = 8 + p % 9, so a query holds a handful of partials, far
+                                                     inside K_gen's pools: pool_regrows stays 0), which plans on
+                                                     K_gen; native there is one K_gen launch over the merged sequence
+    python tools/mixed_bench.py --plan gen --with-seq --leg native --events 65536 --records table
+                                                     the known cost: one single-stream every-start sequence (kept on
+                                                     K_gen by SDH_FLAG_FORCE_GEN) beside them, whose run pushes walk
+                                                     in event chunks and whose native call does not
+
 One JSON line per leg: ms_per_call is the median wall time of --calls calls after --warmup untimed ones,
 the engine's stream drained inside the timed region; the match table is polled (on the device) outside it.
 """
@@ -28,6 +40,9 @@ import time
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--leg", choices=["all", "native", "split"], default="all")
+ap.add_argument("--plan", choices=["chain", "gen"], default="chain")
+ap.add_argument("--with-seq", action="store_true", help="--plan gen: add the single-stream sequence (SDH_FLAG_FORCE_GEN)")
+ap.add_argument("--tile", type=int, default=0, help="--plan gen: SDH_MIX_GEN_TILE (events staged at a time; 1: unstaged)")
 ap.add_argument("--patterns", type=int, default=1000)
 ap.add_argument("--events", type=int, default=65536)
 ap.add_argument("--calls", type=int, default=12)
@@ -40,7 +55,7 @@ a = ap.parse_args()
 
 if a.leg == "all":
     base = [sys.executable, __file__, "--patterns", str(a.patterns), "--calls", str(a.calls), "--warmup", str(a.warmup),
-            "--root", a.root]
+            "--root", a.root, "--plan", a.plan]
     legs = [["--leg", "native", "--events", "2048"], ["--leg", "native", "--events", "65536"],
             ["--leg", "native", "--events", "2048", "--records", "table"],
             ["--leg", "native", "--events", "65536", "--records", "table"],
@@ -63,14 +78,22 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from siddhi_amd import ql  # noqa: E402
-from siddhi_amd.engine import SDH_FLAG_DEVICE_MATCHES, EngineError, HipEngine  # noqa: E402
+from siddhi_amd.engine import SDH_FLAG_DEVICE_MATCHES, SDH_FLAG_FORCE_GEN, EngineError, HipEngine  # noqa: E402
 from siddhi_amd.events import StringDictionary  # noqa: E402
 from siddhi_amd.planner import plan  # noqa: E402
 from siddhi_amd.workloads import c2_threshold_text, stock_events  # noqa: E402
 
 COLS = "(symbol string, price float, volume int)"
 src = [f"define stream A {COLS}; define stream B {COLS};"]
-for p in range(a.patterns):
+for p in range(a.patterns if a.plan == "gen" else 0):
+    t10 = 200 + (p % 750)
+    src.append(f"@info(name='p{p}') from every e1=A[price > {c2_threshold_text(p)}] -> e2=B[price > e1.price] and "
+               f"e3=A[price > {(t10 + 20) // 10}.{t10 % 10}] within {8 + p % 9} milliseconds "
+               f"select e1.price as p1, e3.price as p3 insert into OutStream;")
+if a.with_seq:
+    src.append("@info(name='seq') from every e1=A[price > 50], e2=A[price > e1.price], e3=A[price > e2.price] "
+               "select e1.price as p1, e3.price as p3 insert into OutStream;")
+for p in range(a.patterns if a.plan == "chain" else 0):
     src.append(f"@info(name='p{p}') from every e1=A[price > {c2_threshold_text(p)}] -> e2=B[price > e1.price] "
                f"within {1 + p % 10} sec select e1.price as p1, e2.price as p2 insert into OutStream;")
 ir = plan(ql.parse(" ".join(src)))
@@ -78,11 +101,15 @@ d = StringDictionary()
 blob = ir.serialize([d.intern(s) for s in ir.strings])
 split = a.leg == "split"
 records = "table" if split else a.records
-out = {"leg": a.leg, "patterns": a.patterns, "events": a.events, "records": records, "root": a.root}
+out = {"leg": a.leg, "plan": a.plan, "patterns": a.patterns, "events": a.events, "records": records, "root": a.root}
+debug = {"SDH_MIX_SPLIT": 1} if split else {}
+if a.tile:
+    debug["SDH_MIX_GEN_TILE"] = a.tile
+    out["tile"] = a.tile
 try:
     eng = HipEngine(blob, stream_types=[s.attr_types for s in ir.streams],
-                    flags=SDH_FLAG_DEVICE_MATCHES if records == "device" else 0,
-                    debug={"SDH_MIX_SPLIT": 1} if split else None)
+                    flags=(SDH_FLAG_DEVICE_MATCHES if records == "device" else 0) | (SDH_FLAG_FORCE_GEN if a.with_seq else 0),
+                    debug=debug or None)
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(17)
     ms, matches, runs = [], 0, 0
