@@ -24,7 +24,7 @@
  *                          chains (the StateEvent contents of StateEvent.java:138-182)
  *   sdh_engine_poll_records the matches as the kernels wrote them, left in HBM for a device consumer
  *                          (SDH_FLAG_DEVICE_MATCHES; the formats are documented below)
- *   sdh_engine_retain_events / sdh_engine_poll_rows / sdh_engine_query_outputs
+ *   sdh_engine_retain_events / sdh_engine_poll_rows / sdh_engine_query_outputs / sdh_engine_records_rows
  *                       <- query/selector/QuerySelector.java:76-169 (process: the `select` list evaluated
  *                          over each completed StateEvent): the output rows, projected on the device from
  *                          an event store in HBM
@@ -321,7 +321,7 @@ int sdh_engine_poll_compact_ex(sdh_engine* e, int32_t device, sdh_matches_compac
  * store -- raise sdh_engine_retain_events; the matches stay pending and sdh_engine_poll still returns
  * them. device != 0 leaves every array in engine-owned HBM (valid until the next push / poll /
  * destroy); otherwise they are engine-owned host buffers. With SDH_FLAG_DEVICE_MATCHES n is 0, as for
- * the other polls. */
+ * the other polls: there sdh_engine_records_rows (below) projects the push's device records. */
 typedef struct sdh_rows {
   int64_t n;              /* rows, in sdh_engine_poll's order                         */
   int32_t width;          /* cells per row: the most outputs any query has            */
@@ -429,6 +429,30 @@ int sdh_engine_poll_records(sdh_engine* e, sdh_records* out);
  * a 2-state match). rows == NULL: *n = the row count only; otherwise rows holds cap rows and
  * SDH_E_CAPACITY is returned if the part has more. */
 int sdh_engine_records_compact(sdh_engine* e, int32_t* rows, int64_t cap, int32_t width, int64_t* n);
+/* Output rows from device records (SDH_FLAG_DEVICE_MATCHES after sdh_engine_retain_events): rows
+ * [first, first + max_rows) of the last push's device records, each projected through its query's
+ * `select` list as sdh_engine_poll_rows does; *total = the push's rows (= sdh_records.n). One push can
+ * hold more rows than fit in memory at once, so the caller reads it in windows.
+ * Row order is RECORD order, not the reference's delivery order (R18) -- a consumer that needs that order
+ * polls in the normal mode (sdh_engine_poll_rows):
+ *   part 1 first, block by block and entry by entry (the rows of sdh_engine_records_compact);
+ *   then part 2 in buffer order, pad records skipped;
+ *   then part 3, segment by segment and record by record.
+ * out is an sdh_rows with out->n = clamp(*total - first, 0, max_rows) (max_rows == 0: *total only, no
+ * arrays): seq[i] is the trigger's seq; ts[i] what sdh_engine_poll_rows gives the same match -- the
+ * trigger's ts word of the event store for part 1 and the narrow records of part 2, the record's own ts
+ * for full records and K_chain records; cells / nulls as there (cells[c * out->n + i]).
+ * Nothing is consumed: the call may be repeated with any window, before or after
+ * sdh_engine_poll_records, until the next push / restore / destroy, and returns the same rows each time.
+ * The arrays are engine-owned, sized by max_rows and reused by the next call (device != 0: HBM; otherwise
+ * host buffers they are copied to), valid until then.
+ * Failures change nothing: SDH_E_INVALID without SDH_FLAG_DEVICE_MATCHES, without a prior
+ * sdh_engine_retain_events, or with first < 0 or max_rows < 0; SDH_E_UNSUPPORTED when a query selects more
+ * than 64 outputs; SDH_E_CAPACITY when a row names an event that has left the store (retain more before
+ * the push) or the window's arrays cannot be allocated (ask for fewer rows). sdh_engine_poll_rows keeps
+ * returning n = 0 in this mode. */
+int sdh_engine_records_rows(sdh_engine* e, int64_t first, int64_t max_rows, int32_t device, sdh_rows* out,
+                            int64_t* total);
 /* Absent patterns (`not S[..] for T`) and time. The runtime starts at t (SiddhiAppRuntime.start:
  * start states with a 'for' time schedule their first check at t + T); without this call it starts
  * with its first event or advance. sdh_engine_advance_time: time passes to t with no event, and

@@ -11,6 +11,7 @@
 #include "engine_int.h"
 #include "launchers.h"
 #include "mix_plan.h"
+#include "rec_rows.h"
 
 namespace {
 
@@ -585,6 +586,7 @@ int do_push(sdh_engine* e, int32_t stream, const sdh_batch* b) {
   e->g_dev_matches = 0;
   e->g_used = 0;
   e->dev_polled = false;
+  e->rr_ready = 0;
   e->last_n = b->n;
   e->last_seq_base = B.seq_base;
   for (auto& k : e->part_kept) k = b->n;
@@ -883,6 +885,7 @@ void mix_native(sdh_engine* e, int n_parts, const sdh_mixed_part* parts, const i
   e->g_dev_matches = 0;
   e->g_used = 0;
   e->dev_polled = false;
+  e->rr_ready = 0;
   e->last_n = total;
   e->last_seq_base = B.seq_base;
   for (auto& k : e->part_kept) k = total;
@@ -1493,6 +1496,7 @@ void time_advance(sdh_engine* e, int64_t t) {
   e->g_dev_matches = 0;
   e->g_used = 0;
   e->dev_polled = false;
+  e->rr_ready = 0;
   e->last_n = 0;
   e->last_seq_base = e->seq;
   double ms = 0, bytes = 0;
@@ -2176,6 +2180,156 @@ int sdh_engine_records_compact(sdh_engine* e, int32_t* rows, int64_t cap, int32_
   });
 }
 
+// sdh_engine_records_rows: rows [first, first + max_rows) of the last push's device records, in record
+// order (rec_rows.h), each projected through its query's select list. Nothing is consumed: the records
+// stay as they are, and what locates a row in them (the blocks' row offsets, the flat records' heads, the
+// segments' first rows) is made once per push and kept until the next.
+static int do_records_rows(sdh_engine* e, int64_t first, int64_t max_rows, bool device, sdh_rows* out, int64_t* total) {
+  check_usable(e);
+  if (!(e->cfg.flags & SDH_FLAG_DEVICE_MATCHES))
+    throw Error(SDH_E_INVALID, "sdh_engine_records_rows needs SDH_FLAG_DEVICE_MATCHES (use sdh_engine_poll_rows)");
+  if (!e->ev_cap) throw Error(SDH_E_INVALID, "sdh_engine_records_rows: no events are kept (sdh_engine_retain_events)");
+  if (first < 0 || max_rows < 0) throw Error(SDH_E_INVALID, "sdh_engine_records_rows: a negative window");
+  const auto& S = e->selp;
+  if (S.over >= 0)
+    throw Error(SDH_E_UNSUPPORTED, fmt("query %d selects more than %d outputs", S.over, sel::MAXOUT));
+  if (S.bad) throw Error(SDH_E_INVALID, "a select list names a slot or an attribute its query lacks, or holds an unknown opcode");
+  if (S.max_depth > kg::GSTACK - 1)
+    throw Error(SDH_E_UNSUPPORTED, "a select expression is too deep for the device evaluation stack");
+  HIPCHK(hipSetDevice(e->dev));
+  const int nb = e->r_placing ? 0 : e->r_blocks_used;
+  const rr::Parts P{{nb > 0 ? e->r_matches : 0, e->g_dev_matches, e->device_matches}};
+  const int64_t all = P.total();
+  const int64_t n = std::max<int64_t>(0, std::min(all - first, max_rows));
+  const int width = S.width;
+  const size_t cw = (size_t)std::max(1, width);
+  if (n) {
+    try {
+      e->rr_q.ensure((size_t)n);
+      e->rr_ts.ensure((size_t)n);
+      e->rr_seq.ensure((size_t)n);
+      e->rr_nulls.ensure((size_t)n);
+      e->rr_cells.ensure((size_t)n * cw);
+      if (!device) {
+        e->hrr_q.ensure((size_t)n);
+        e->hrr_ts.ensure((size_t)n);
+        e->hrr_seq.ensure((size_t)n);
+        e->hrr_nulls.ensure((size_t)n);
+        e->hrr_cells.ensure((size_t)n * cw);
+      }
+    } catch (const Error& ex) {
+      if (ex.code != SDH_E_DEVICE) throw;
+      (void)hipGetLastError();
+      throw Error(SDH_E_CAPACITY, fmt("no device memory for a window of %lld rows: ask for fewer (max_rows)", (long long)n));
+    }
+    e->pr_err.ensure(1);
+    const sel::Tables T{e->d_sel_code.p, e->d_sel_outs.p, e->d_sel_shapes.p, e->d_sel_queries.p, e->d_sel_consts.p};
+    const sel::Store st{e->ev_rows.p, e->ev_cap - 1, std::max(e->ev_first, e->seq - e->ev_cap), e->ev_w, 0};
+    const int deep = S.max_depth > kg::RSTACK;
+    const int search = sdh::knob("SDH_RR_SEARCH") ? 1 : 0;
+    HIPCHK(hipMemsetAsync(e->pr_err.p, 0, 4, e->stream));
+    for (int p = 0; p < 3; ++p) {
+      RecRows R{};
+      R.n = rr::part_window(P, p, first, n, R.first);
+      if (R.n <= 0) continue;
+      R.out0 = P.first(p) + R.first - first;
+      if (p == 0) {
+        if (!(e->rr_ready & 1)) {  // the blocks' first rows (as sdh_engine_records_compact)
+          e->d_rrow_off.ensure((size_t)nb + 1);
+          e->d_rrow_tmp.ensure(sdh_ratchet_compact_temp(nb));
+          HIPCHK(sdh_ratchet_compact(e->d_rmatch.p, e->r_blk_recs, e->r_wide, e->d_blk_count.p, e->d_blk_group.p,
+                                     e->d_blk_side.p, e->d_rg.p, e->r_seq_base, nb, e->d_rrow_off.p, e->d_rrow_tmp.p,
+                                     e->d_rrow_tmp.n, 4, nullptr, e->stream));
+          e->rr_ready |= 1;
+        }
+        R.seq_base = e->r_seq_base;
+        R.match = e->d_rmatch.p;
+        R.blk_recs = e->r_blk_recs;
+        R.wide = e->r_wide;
+        R.blk_count = e->d_blk_count.p;
+        R.blk_group = e->d_blk_group.p;
+        R.blk_side = e->d_blk_side.p;
+        R.groups = e->d_rg.p;
+        R.row_off = e->d_rrow_off.p;
+        R.nb = nb;
+      } else if (p == 1) {
+        if (!(e->rr_ready & 2)) {  // the records' heads: one walk of the buffer per push
+          e->rr_rec_off.ensure((size_t)P.n[1]);
+          e->rr_heads.ensure(1);
+          e->rr_tmp.ensure(sdh_flat_heads_temp(e->g_used));
+          HIPCHK(sdh_flat_heads(e->g_out.p, e->g_used, e->rr_tmp.p, e->rr_rec_off.p, P.n[1], e->rr_heads.p, e->stream));
+          unsigned long long heads = 0;
+          d2h_sync(e, &heads, e->rr_heads.p, 8);
+          if ((int64_t)heads != P.n[1])
+            throw Error(SDH_E_DEVICE, fmt("the flat records hold %llu heads, the push counted %lld", heads, (long long)P.n[1]));
+          e->rr_ready |= 2;
+        }
+        R.seq_base = e->last_seq_base;
+        R.flat = e->g_out.p;
+        R.rec_off = e->rr_rec_off.p;
+      } else {
+        const int64_t ni = (int64_t)e->work.size();
+        if (!(e->rr_ready & 4)) {  // the segments' first rows
+          std::vector<int64_t> so((size_t)ni), row((size_t)ni + 1, 0);
+          if (ni) d2h_sync(e, row.data() + 1, e->d_seg_count.p, (size_t)ni * 8);
+          for (int64_t i = 0; i < ni; ++i) {
+            so[(size_t)i] = e->work[(size_t)i].seg_off;
+            row[(size_t)i + 1] += row[(size_t)i];
+          }
+          if (row[(size_t)ni] != P.n[2])
+            throw Error(SDH_E_DEVICE, fmt("the K_chain segments hold %lld records, the push counted %lld",
+                                          (long long)row[(size_t)ni], (long long)P.n[2]));
+          upload(e->rr_seg_off, so);
+          upload(e->rr_seg_row, row);
+          e->rr_ready |= 4;
+        }
+        R.seq_base = e->last_seq_base;
+        R.chain = e->d_match.p;
+        R.seg_off = e->rr_seg_off.p;
+        R.seg_row = e->rr_seg_row.p;
+        R.items = ni;
+        R.rec_words = e->rec_words;
+        R.qinfo = e->d_qinfo.p;
+      }
+      HIPCHK(sdh_select_records(&T, &st, deep, p, search, &R, n, width, e->rr_q.p, e->rr_ts.p, e->rr_seq.p,
+                                e->rr_cells.p, e->rr_nulls.p, e->pr_err.p, e->stream));
+    }
+    int32_t bad = 0;
+    d2h_sync(e, &bad, e->pr_err.p, 4);
+    if (bad)
+      throw Error(SDH_E_CAPACITY, fmt("a record reads an event that has left the event store of %lld events: raise "
+                                      "sdh_engine_retain_events before the push",
+                                      (long long)e->ev_cap));
+    if (!device) {
+      HIPCHK(hipMemcpyAsync(e->hrr_q.p, e->rr_q.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->hrr_ts.p, e->rr_ts.p, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->hrr_seq.p, e->rr_seq.p, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(e->hrr_nulls.p, e->rr_nulls.p, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+      if (width)
+        HIPCHK(hipMemcpyAsync(e->hrr_cells.p, e->rr_cells.p, (size_t)n * width * 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipStreamSynchronize(e->stream));
+    }
+  }
+  *total = all;
+  *out = sdh_rows{};
+  out->n = n;
+  out->width = width;
+  if (n) {
+    out->query = device ? e->rr_q.p : e->hrr_q.p;
+    out->ts = device ? e->rr_ts.p : e->hrr_ts.p;
+    out->seq = device ? e->rr_seq.p : e->hrr_seq.p;
+    out->cells = device ? e->rr_cells.p : e->hrr_cells.p;
+    out->nulls = device ? e->rr_nulls.p : e->hrr_nulls.p;
+  }
+  return SDH_OK;
+}
+
+int sdh_engine_records_rows(sdh_engine* e, int64_t first, int64_t max_rows, int32_t device, sdh_rows* out,
+                            int64_t* total) {
+  if (!e || !out || !total) return SDH_E_INVALID;
+  return guard(e, [&]() { return do_records_rows(e, first, max_rows, device != 0, out, total); });
+}
+
 int sdh_engine_push_stats(sdh_engine* e, double* last_kernel_ms, double* last_kernel_bytes) {
   if (!e || !last_kernel_ms || !last_kernel_bytes) return SDH_E_INVALID;
   *last_kernel_ms = e->stats.last_kernel_ms;  // (host-side values: no device work, no sync)
@@ -2282,6 +2436,7 @@ int sdh_engine_restore(sdh_engine* e, const void* blob, size_t len) {
     e->device_matches = 0;
     e->r_matches = 0;
     e->r_blocks_used = 0;
+    e->rr_ready = 0;
     table_clear(e);
     e->broken.clear();
     return SDH_OK;

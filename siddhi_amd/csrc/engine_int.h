@@ -259,6 +259,19 @@ struct sdh_engine {
   HostBuf<int32_t> hr_q;
   HostBuf<int64_t> hr_cells;
   HostBuf<uint64_t> hr_nulls;
+  // sdh_engine_records_rows: the window's rows (sized by max_rows, reused across calls) and what a push's
+  // records need once to be located by row -- the flat records' word offsets (select.hip
+  // flat_heads_kernel) and the K_chain segments' first rows; rr_ready: bit p = part p's is made
+  DevBuf<int32_t> rr_q;
+  DevBuf<int64_t> rr_ts, rr_seq, rr_cells;
+  DevBuf<uint64_t> rr_nulls;
+  HostBuf<int32_t> hrr_q;
+  HostBuf<int64_t> hrr_ts, hrr_seq, hrr_cells;
+  HostBuf<uint64_t> hrr_nulls;
+  DevBuf<int64_t> rr_rec_off, rr_seg_off, rr_seg_row;
+  DevBuf<unsigned long long> rr_heads;
+  DevBuf<uint8_t> rr_tmp;            // (the walk's tables: 6 bytes per word of the flat buffer)
+  int rr_ready = 0;
   // ---- K_gen (general interpreter) ----
   kg::LProgram lp;                   // full IR (receivers, runtime tree, partitions)
   std::vector<int> out_rank;         // R18 rank per (query, stream)

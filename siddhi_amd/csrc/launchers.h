@@ -46,6 +46,37 @@ extern "C" hipError_t sdh_select_placed(const sdh::sel::Tables* T, const sdh::se
                                         int width, int32_t* oq, int64_t* ots, int64_t* oseq, int64_t* cells,
                                         uint64_t* nulls, int32_t* err, hipStream_t s);
 
+// rows from device records (sdh_engine_records_rows): one part's rows [first, first + n) of the last
+// push's records into rows [out0, out0 + n) of the window's arrays
+namespace sdh {
+struct RecRows {
+  int64_t first, n, out0, seq_base;
+  const int64_t* match;  // K_ratchet blocks
+  int32_t blk_recs, wide;
+  const int32_t* blk_count;
+  const int32_t* blk_group;
+  const int32_t* blk_side;
+  const RatchetGroup* groups;
+  const int64_t* row_off;
+  int64_t nb;
+  const int64_t* flat;   // flat records
+  const int64_t* rec_off;
+  const int64_t* chain;  // K_chain segments
+  const int64_t* seg_off;
+  const int64_t* seg_row;
+  int64_t items;
+  int32_t rec_words, pad;
+  const int32_t* qinfo;
+};
+}  // namespace sdh
+extern "C" hipError_t sdh_select_records(const sdh::sel::Tables* T, const sdh::sel::Store* st, int deep, int part,
+                                         int search, const sdh::RecRows* R, int64_t n_out, int width, int32_t* oq,
+                                         int64_t* ots, int64_t* oseq, int64_t* cells, uint64_t* nulls, int32_t* err,
+                                         hipStream_t s);
+extern "C" size_t sdh_flat_heads_temp(int64_t words);
+extern "C" hipError_t sdh_flat_heads(const int64_t* out, int64_t words, void* temp, int64_t* rec_off, int64_t cap,
+                                     unsigned long long* n_out, hipStream_t s);
+
 extern "C" hipError_t sdh_launch_gen(const sdh::GenLaunch* L, hipStream_t s);
 extern "C" hipError_t sdh_launch_part(const sdh::PartLaunch* L, hipStream_t s);
 // the interpreted kernel of K_part's chain kind (nfa_part_chain.hip; sdh_launch_part hands PK_CHAIN on)

@@ -151,7 +151,7 @@ EXPORTS = ["sdh_engine_create", "sdh_engine_push", "sdh_engine_flush", "sdh_engi
            "sdh_engine_gather", "sdh_engine_reserve", "sdh_engine_reserve_keys", "sdh_engine_poll_records",
            "sdh_engine_records_compact", "sdh_engine_debug_shared_pushes", "sdh_engine_retain_events",
            "sdh_engine_poll_rows", "sdh_engine_query_outputs", "sdh_engine_push_mixed",
-           "sdh_engine_debug_mixed_pushes"]
+           "sdh_engine_debug_mixed_pushes", "sdh_engine_records_rows"]
 SDH_COMM_ID_BYTES = 128
 
 _lib = None
@@ -220,6 +220,9 @@ def load_library(path: str = LIB_PATH):
         lib.sdh_engine_push_mixed.argtypes = [P, ctypes.c_int32, ctypes.POINTER(SdhMixedPart), P, ctypes.c_int64,
                                               ctypes.c_int32]
         lib.sdh_engine_debug_mixed_pushes.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
+    if hasattr(lib, "sdh_engine_records_rows"):  # (as above: an older build lacks it)
+        lib.sdh_engine_records_rows.argtypes = [P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                                ctypes.POINTER(SdhRows), ctypes.POINTER(ctypes.c_int64)]
     _lib = lib
     return lib
 
@@ -485,6 +488,31 @@ class HipEngine:
         return (np.ctypeslib.as_array(r.query, shape=(n,)).copy(), np.ctypeslib.as_array(r.ts, shape=(n,)).copy(),
                 np.ctypeslib.as_array(r.seq, shape=(n,)).copy(), cells,
                 np.ctypeslib.as_array(r.nulls, shape=(n,)).copy())
+
+    def records_rows(self, first: int = 0, max_rows: Optional[int] = None, device: bool = False):
+        """Rows [first, first + max_rows) of the last push's device records, in record order, projected
+        through their queries' select lists (sdh_engine_records_rows; SDH_FLAG_DEVICE_MATCHES after
+        retain_events): what poll_rows returns -- host arrays (query, ts, seq, cells[width, n], nulls), or
+        the SdhRows struct of HBM pointers when device is set -- plus the push's row count `total`.
+        max_rows None: every row from `first` on; 0: `total` only. Nothing is consumed."""
+        r = SdhRows()
+        total = ctypes.c_int64()
+        if max_rows is None:
+            self._check(self.lib.sdh_engine_records_rows(self.h, int(first), 0, int(device), ctypes.byref(r),
+                                                         ctypes.byref(total)))
+            max_rows = max(0, total.value - int(first))
+        self._check(self.lib.sdh_engine_records_rows(self.h, int(first), int(max_rows), int(device), ctypes.byref(r),
+                                                     ctypes.byref(total)))
+        if device:
+            return r, total.value
+        n, w = r.n, r.width
+        if n == 0:
+            return (np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((w, 0), np.int64),
+                    np.zeros(0, np.uint64), total.value)
+        cells = np.ctypeslib.as_array(r.cells, shape=(w, n)).copy() if w else np.zeros((0, n), np.int64)
+        return (np.ctypeslib.as_array(r.query, shape=(n,)).copy(), np.ctypeslib.as_array(r.ts, shape=(n,)).copy(),
+                np.ctypeslib.as_array(r.seq, shape=(n,)).copy(), cells,
+                np.ctypeslib.as_array(r.nulls, shape=(n,)).copy(), total.value)
 
     def query_outputs(self, q: int) -> List[int]:
         """The ir.T_* type of each output of query q's select list (sdh_engine_query_outputs)."""
